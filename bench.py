@@ -13,7 +13,13 @@ KKT weights for top/bottom-10 books on every test date + PnL/turnover scan (KKT:
 streams: AlphaSignalAnalyzer on the predictions (KKT:630-631) and the per-date FM30 OLS +
 Fama-MacBeth (north-star extension).
 
-Usage: python bench.py [--gpus N --steps K --warmup W].  N > 1 runs one rank per GPU: under
+Usage: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full].  A plain run
+sets up, warms up, times the K steps and prints the headline line (with the rooflines its own
+events give); ``--full`` adds every secondary line: the top_n_100 / dense_lasso variants, configs
+B / D / E and the two CPU baselines (each can be dropped again with its ``--no-...`` option).
+``--dump-outputs DIR`` writes what the last timed step computed as ``DIR/<name>.npy`` (float64;
+the two panel-sized planes as a fixed seeded sample of cells; NaN / inf cells as 0 there and
+coded in ``DIR/<name>_nonfinite.npy``).  N > 1 runs one rank per GPU: under
 torch.distributed.run (WORLD_SIZE set; --gpus must equal it), or, started bare, bench.py starts
 ``python -m torch.distributed.run --nproc-per-node N ... bench.py`` itself as a CHILD process
 before anything imports torch or touches the GPU, passes rank 0's line through and exits with
@@ -376,6 +382,63 @@ def variant_line(grid, cfg, steps: int, warmup: int, what: str, roof=None) -> di
     return out
 
 
+# --dump-outputs: cells sampled from the two panel-sized outputs (fixed seed: the same cells in
+# every run of the same arguments), and the cap on everything written
+DUMP_SEED = 20231
+DUMP_FACTOR_CELLS = 2_000_000
+DUMP_PRED_CELLS = 1_000_000
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(pipe, outdir: str) -> dict:
+    """What a caller of ``pipe.step()`` reads after the step, as ``outdir/<name>.npy`` (float64):
+    the Lasso fit, the rebalance books / weights / sums / status, the PnL series, the
+    Fama-MacBeth betas and statistics, the analyzer series -- each in full -- and fixed seeded
+    samples of the two panel-sized planes: the factor panel (cells of this rank's asset shard,
+    any date) and the predictions (cells on the test dates).  NaN and +-inf are values of these
+    results (a cell before its warm-up, a date without a forward return, a prediction off the
+    z-score rows), so each array goes out as two files of finite numbers: ``<name>.npy`` with 0
+    in those cells and ``<name>_nonfinite.npy`` (float32) with 0 = finite, 1 = NaN, 2 = +inf,
+    3 = -inf.  Returns {name: shape}."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    full = {"lasso_beta": pipe.lasso_beta, "lasso_info": pipe.lasso_info,
+            "fm_beta": pipe.fm_beta, "fm_nobs": pipe.fm_nobs, "fm_rank": pipe.fm_rank,
+            "fm_mean": pipe.fm_mean, "fm_t": pipe.fm_t}
+    full.update({"pnl_" + k: v for k, v in pipe.pnl.items()})
+    full.update({"reb_" + k: pipe.reb[k] for k in ("k", "books", "weights", "sums", "status")})
+    if pipe.cfg.analyzer:
+        full.update({"an_" + k: pipe.an[k] for k in ("ic", "layer_mean", "layer_cnt", "port",
+                                                     "cum_layer", "ls", "cum_port", "ir")})
+    arrays = {k: v.detach().to(torch.float64).cpu().numpy() for k, v in full.items()}
+    rng = np.random.default_rng(DUMP_SEED)
+    dev = pipe.out.device
+    nf, T = int(pipe.out.shape[0]), pipe.T
+    if pipe.A_r > 0:
+        n = min(DUMP_FACTOR_CELLS, nf * T * pipe.A_r)
+        idx = [torch.from_numpy(rng.integers(0, hi, size=n)).to(dev) for hi in (nf, T, pipe.A_r)]
+        arrays["factors_sample"] = pipe.out[idx[0], idx[1], idx[2]].cpu().numpy()
+    s0 = pipe.sp.s0
+    n = min(DUMP_PRED_CELLS, (T - s0) * pipe.A)
+    idx = [torch.from_numpy(rng.integers(lo, hi, size=n)).to(dev)
+           for lo, hi in ((s0, T), (0, pipe.A))]
+    arrays["pred_sample"] = pipe.pred[idx[0], idx[1]].cpu().numpy()
+    files = {}
+    for k, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        code = (np.isnan(a) + 2 * np.isposinf(a) + 3 * np.isneginf(a)).astype(np.float32)
+        files[k] = np.where(code == 0, a, 0.0)
+        files[k + "_nonfinite"] = code
+    total = sum(a.nbytes for a in files.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (cap "
+                         f"{DUMP_MAX_BYTES})")
+    for k, a in files.items():
+        np.save(os.path.join(outdir, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def _free_port() -> int:
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -454,13 +517,22 @@ def main():
     ap.add_argument("--reb-split", type=int, default=None,
                     help="PipelineConfig.reb_split (N > 1: 1 = rebalance dates split over the "
                          "ranks + all-gather, 0 = every rank all dates)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed as "
+                         "DIR/<name>.npy (float64; panel-sized planes as a fixed seeded sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the headline run, also the secondary lines -- top_n_100 / "
+                         "dense_lasso variants, configs B / D / E, the CPU baselines (see "
+                         "--no-variants, --no-configs, --no-cpu-baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the two CPU baseline lines")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the config B / D / E lines (N = 1 only)")
+                    help="with --full: skip the config B / D / E lines (N = 1 only)")
     ap.add_argument("--config-only", choices=("b", "d", "e"), default=None,
                     help="run only that config line and print it (profiling runs)")
     ap.add_argument("--no-variants", action="store_true",
-                    help="skip the top_n_100 / dense_lasso secondary lines (N = 1 only)")
+                    help="with --full: skip the top_n_100 / dense_lasso secondary lines "
+                         "(N = 1 only)")
     args = ap.parse_args()
     world, spawn = launch_world(args.gpus)
     if spawn and not args.config_only:
@@ -539,7 +611,7 @@ def main():
     for _ in range(args.warmup):
         pipe.step()
     torch.cuda.synchronize()
-    if rank == 0 and args.warmup:
+    if rank == 0 and args.warmup and args.full:
         s = pipe.summary()
         log(f"[rank 0] warmup: final value {s['final_value']:.9g}, sharpe {s['sharpe']:.6g}, "
             f"lasso n_iter {s['lasso_n_iter']} nnz {s['lasso_nnz']}, FM rank counts "
@@ -569,6 +641,11 @@ def main():
                          device="cpu" if backend == "gloo" else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t[0])
+
+    if rank == 0 and args.dump_outputs:
+        shapes = dump_outputs(pipe, args.dump_outputs)
+        log(f"[rank 0] --dump-outputs {args.dump_outputs}: " +
+            ", ".join(f"{k}{tuple(v)}" for k, v in shapes.items()))
 
     if args.emulate_world > 1:          # per-rank proxy: no headline line
         ms = elapsed / args.steps * 1e3
@@ -616,7 +693,7 @@ def main():
             # the portfolio's last value after the timed steps (KKT:892): the same for every N
             "final_value": final_value,
         }
-        if world == 1 and not args.no_variants:
+        if world == 1 and args.full and not args.no_variants:
             # secondary lines the headline step never exercises: the active-set KKT QP on
             # 100-name books (SURVEY §8(d) config C stress), and a dense Lasso / predict (a
             # stated non-reference design: the 96 factors without tmr_ret1d, KKT:433-443)
@@ -632,14 +709,14 @@ def main():
                 grid, replace(cfg, features=DENSE_FEATURES, alpha=DENSE_ALPHA), vs, vw,
                 f"variant of KKT:433-443 / KKT:605: features without tmr_ret1d (96 columns), "
                 f"Lasso alpha {DENSE_ALPHA:g} -- a dense fit, so the predict reads its support")
-        if world == 1 and not args.no_configs:
+        if world == 1 and args.full and not args.no_configs:
             # the other BASELINE configs' throughput (north_star: "throughput across the
             # configs"), each on its own resident synthetic panel
             cs, cw = max(2, min(args.steps, 5)), 1
             res["config_b"] = config_b_line(args.seed, cs, cw)
             res["config_d"] = config_d_line(args.seed, 2)
             res["config_e"] = config_e_line(args.seed, 3)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(args.seed)
             res["cpu_baseline_port"] = cpu_port(args.seed)
         print(json.dumps(res), flush=True)

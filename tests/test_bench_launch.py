@@ -91,7 +91,7 @@ def test_bench_line_contract():
     higher_is_better / scaling / vs_baseline / dtype / data / config) plus the roofline and
     cpu_baseline objects, with consistent numbers."""
     env = dict(os.environ)
-    args = [a for a in SMALL if a != "--no-cpu-baseline"]
+    args = [a for a in SMALL if a != "--no-cpu-baseline"] + ["--full"]
     r = subprocess.run([sys.executable, "-u", BENCH] + args, cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=540)
     assert r.returncode == 0, r.stderr[-4000:]
@@ -118,3 +118,46 @@ def test_bench_line_contract():
         assert k in cb, k
     assert cb["value"] > 0 and cb["cores"] == 1 and cb["kind"] in ("port", "reference")
 
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain one-GPU run (no --full): the headline line only -- none of the secondary lines --
+    and ``--dump-outputs DIR`` leaves the last timed step's results as ``.npy`` files of finite
+    float64 values (and float32 NaN / inf codes) of at most 64 MB in all, the PnL series ending
+    on the line's ``final_value``."""
+    import numpy as np
+    plain = [a for a in SMALL if not a.startswith("--no-")]
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, "-u", BENCH, "--gpus", "1"] + plain +
+                       ["--dump-outputs", str(out)], cwd=ROOT, env=dict(os.environ),
+                       capture_output=True, text=True, timeout=540)
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [s for s in r.stdout.splitlines() if s.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    for k in ("top_n_100", "dense_lasso", "config_b", "config_d", "config_e", "cpu_baseline",
+              "cpu_baseline_port"):
+        assert k not in d, k
+    files = sorted(out.glob("*.npy"))
+    arrs = {f.stem: np.load(f) for f in files}
+    for k in ("factors_sample", "pred_sample", "lasso_beta", "pnl_value", "reb_weights",
+              "fm_beta", "an_ic"):
+        assert k in arrs, k
+    assert all(a.dtype in (np.float64, np.float32) and a.size > 0 for a in arrs.values())
+    # every file holds finite numbers only: NaN / inf cells are 0 in <name>.npy and coded
+    # 1 / 2 / 3 in <name>_nonfinite.npy
+    assert all(np.isfinite(a).all() for a in arrs.values())
+    for k, a in arrs.items():
+        if not k.endswith("_nonfinite"):
+            code = arrs[k + "_nonfinite"]
+            assert a.dtype == np.float64 and code.shape == a.shape
+            assert np.isin(code, (0, 1, 2, 3)).all() and not a[code != 0].any()
+    assert sum(f.stat().st_size for f in files) <= 64 * 1000 * 1000
+    assert arrs["pnl_value"][-1] == d["final_value"]
+    # the samples hit computed cells, not only the NaN cells of the planes
+    assert (arrs["factors_sample_nonfinite"] == 0).mean() > 0.5
+    assert (arrs["pred_sample_nonfinite"] == 0).mean() > 0.5

@@ -25,7 +25,7 @@ for step in "$@"; do
       timeout -k 10 300 python -u bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-variants --no-configs > $o/bench.json 2> $o/bench.err || { tail -5 $o/bench.err; exit 1; }
       python3 -c "import json; d=json.load(open('$o/bench.json')); print(d['ms_per_step'], d['value'], 'host', d.get('host_issue_ms_per_step'), {k: round(v, 2) for k, v in d['stage_ms'].items()}); print('roof', d['roofline']['frac'], d['roofline_next']['frac'])" ;;
     full)
-      timeout -k 10 900 python -u bench.py > $o/full.json 2> $o/full.err || { tail -5 $o/full.err; exit 1; }
+      timeout -k 10 900 python -u bench.py --full > $o/full.json 2> $o/full.err || { tail -5 $o/full.err; exit 1; }
       python3 -c "import json; d=json.load(open('$o/full.json')); print(d['ms_per_step'], d['value'], d['stage_ms']); print('roof', d['roofline']['frac'], d['roofline_next']['frac']); [print(k, json.dumps(d[k])[:300]) for k in ('top_n_100', 'dense_lasso', 'config_b', 'config_d', 'config_e', 'cpu_baseline')]" ;;
     emu)
       for w in 8 4 2; do
