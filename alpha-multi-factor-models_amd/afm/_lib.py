@@ -83,6 +83,8 @@ SIGNATURES = {
     "afm_gram_tree_f64": (I32, [P, I32, P, I64, I32, I32, P]),
     "afm_zpredict_f64": (I32, [P, P, I64, I64, I64, I64, P, I32, P, P, P, P]),
     "afm_lasso_fit_f64": (I32, [P, P, P, I32, DBL, I32, DBL, I32, P, P]),
+    "afm_lasso_batch_f64": (I32, [P, P, I64, P, I64, I32, P, I32, I64, I32, I32, DBL, I32, P, P]),
+    "afm_gram_score_f64": (I32, [P, P, I64, P, I64, I32, P, I32, I64, P]),
 }
 
 

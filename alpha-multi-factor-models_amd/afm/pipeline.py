@@ -990,6 +990,75 @@ class Pipeline:
         mark("analyzer", 1)
 
     # ------------------------------------------------------------------------------------------
+    def _range_gram(self, h, t0, nt, bufs, gram):
+        """The pooled Gram of the z-score rows of the dates [t0, t0 + nt) -> gram [1][p+2][p+2]:
+        the partials and tree of ``_pooled_blocks`` + the block level, in the buffers ``bufs`` (not
+        the step's)."""
+        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
+        T, lda, p = self.T, self.lda_r, self.p
+        part, c1b, rb, blk = bufs
+        blk.zero_()
+        chk(L.afm_zpool_f64(h, P(self.out), T * lda, lda, P(self.feat), None, p, TARGET,
+                            P(self.zs), p, P(self.zrows), t0, nt, 0, self.nrb, self.A_r,
+                            N_CHUNKS, P(part), 0), "zpool")
+        c1, c2 = CHUNK_TREE
+        chk(L.afm_gram_tree_f64(h, p, P(part), self.nrb * N_CHUNKS, c1, 0, P(c1b)), "tree chunks")
+        chk(L.afm_gram_tree_f64(h, p, P(c1b), self.nrb * c2, c2, 0, P(rb)), "tree chunks 2")
+        chk(L.afm_gram_tree_f64(h, p, P(rb), self.nrb, self.rb_per_blk, 0, P(blk)),
+            "tree row-blocks")
+        chk(L.afm_gram_tree_f64(h, p, P(blk), N_BLOCKS, N_BLOCKS, 1, P(gram)), "tree blocks")
+
+    def lasso_cv(self, alphas=None, *, n_alphas: int = 100, eps: float = 1e-3) -> dict:
+        """Validation-scored alpha selection on the last ``step()``'s panel (one GPU): the
+        reference carries a ``valid`` split its linear models never use (KKT:426-427) and fixes
+        alpha = 2e-4 (KKT:605).  The z statistics stay the train window's (KKT:449-454).
+
+        The pooled Grams of train [0, tr1) and valid [v0, v1) are built like the step's (buffers
+        of this call's own); the train Gram walks the alpha grid warm-started in one
+        ``afm_lasso_batch_f64`` launch (``alphas``: descending after sorting; None: scikit-learn's
+        grid of ``n_alphas`` from alpha_max down to ``eps`` alpha_max, on the train Gram); every
+        model is scored on the valid Gram's moments (``afm_gram_score_f64``); the refit at the
+        alpha of least valid MSE runs on the step's train+valid Gram (``pool_g``, train_end
+        counted twice where the reference does).  Returns host arrays: ``alphas``, ``coefs``
+        [n_alphas][p+1] (intercept first), ``n_iter``, ``dual_gap``, ``n_train``, ``n_valid``,
+        ``mse_valid``, ``r2_valid``, ``ic_valid``, ``best``, ``alpha_``, ``beta`` (the refit)."""
+        import torch
+        from .regression import _given_alphas, alpha_grid, gram_score, lasso_batch
+        if self.W > 1:
+            raise NotImplementedError("lasso_cv() runs on one GPU (world = 1)")
+        if self.nrb == 0:
+            raise ValueError("lasso_cv(): the panel has no assets")
+        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
+        c, sp, p = self.cfg, self.sp, self.p
+        if getattr(self, "_cv_bufs", None) is None:
+            self._cv_bufs = tuple(torch.empty_like(b) for b in (self.pool_part, self.pool_c1,
+                                                                self.pool_rb, self.pool_blk))
+            self._cv_gram = torch.empty((2, self.p2, self.p2), dtype=torch.float64,
+                                        device=self.out.device)
+        gram, shift = self._cv_gram, self.pool_s.expand(2, self.p2).contiguous()
+        h = self.ctx.bind_stream()
+        self._range_gram(h, 0, sp.tr1, self._cv_bufs, gram[0:1])
+        self._range_gram(h, sp.v0, sp.v1 - sp.v0, self._cv_bufs, gram[1:2])
+        a = _given_alphas(alphas) if alphas is not None else \
+            alpha_grid(gram[0].cpu().numpy(), p, eps, n_alphas)
+        beta, info = lasso_batch(gram[0:1], shift[0:1], p, torch.from_numpy(a).to(gram.device),
+                                 nprob=1, warm=True, max_iter=c.max_iter, tol=c.lasso_tol)
+        score = gram_score(gram[1:2], shift[1:2], p, beta).cpu().numpy()[0]
+        n_train = float(gram[0, 0, 0].item())
+        best = int(np.argmin(score[:, 1]))
+        refit = torch.empty(p + 1, dtype=torch.float64, device=gram.device)
+        rinfo = torch.empty(3, dtype=torch.float64, device=gram.device)
+        chk(L.afm_lasso_fit_f64(self.ctx.bind_stream(), P(self.pool_g), P(self.pool_s), p,
+                                float(a[best]), c.max_iter, c.lasso_tol, 0, P(refit), P(rinfo)),
+            "lasso refit")
+        info_h = info[0].cpu().numpy()
+        return {"alphas": a, "coefs": beta[0].cpu().numpy(),
+                "n_iter": info_h[:, 2].astype(np.int64), "dual_gap": info_h[:, 0] / n_train,
+                "n_train": int(n_train), "n_valid": int(score[0, 0]),
+                "mse_valid": score[:, 1].copy(), "r2_valid": score[:, 2].copy(),
+                "ic_valid": score[:, 3].copy(), "best": best, "alpha_": float(a[best]),
+                "beta": refit.cpu().numpy()}
+
     def summary(self) -> dict:
         """Host copies of the headline results (after a synchronize)."""
         v = self.pnl["value"].cpu().numpy()

@@ -310,3 +310,198 @@ class Lasso:
         bits[0, :n] = 1
         out = predict_grid(base.view(p, 1, lda), lda, list(range(p)), self._beta, bits, 0, 1)
         return out[0, :n].cpu().numpy()
+
+
+# ---- regularisation paths and validation-scored alpha selection ---------------------------------
+def lasso_batch(gram, shift, p: int, alphas, *, nprob: int = 1, warm: bool = True,
+                max_iter: int = 1000, tol: float = 1e-4, positive: bool = False,
+                shared: bool = False):
+    """Raw binding of afm_lasso_batch_f64 -> (beta [nprob][nalpha][p+1] (intercept first), info
+    [nprob][nalpha][3] = {gap, tol * y'y, n_iter}).  ``gram`` [nprob][p+2][p+2] / ``shift``
+    [nprob][p+2] pooled moments (``shared``: one Gram for every problem); ``alphas``: device
+    float64 [nalpha], sklearn's alpha.  ``warm``: each problem walks the alphas in the order given,
+    every solve started from the previous one's weights; else nprob * nalpha solves from zero."""
+    import torch
+    dev = gram.device
+    nalpha = int(alphas.numel())
+    beta = torch.empty((nprob, nalpha, p + 1), dtype=torch.float64, device=dev)
+    info = torch.empty((nprob, nalpha, 3), dtype=torch.float64, device=dev)
+    P = _lib.ptr
+    h = _lib.Context.get(dev.index).bind_stream()
+    gs, ss = (0, 0) if shared else ((p + 2) * (p + 2), p + 2)
+    _lib.check(_lib.lib().afm_lasso_batch_f64(h, P(gram), gs, P(shift), ss, p, P(alphas), nalpha,
+                                              nprob, int(bool(warm)), int(max_iter), float(tol),
+                                              int(bool(positive)), P(beta), P(info)),
+               "afm_lasso_batch_f64")
+    return beta, info
+
+
+def gram_score(gram, shift, p: int, beta, *, shared: bool = False):
+    """Raw binding of afm_gram_score_f64: models ``beta`` [nprob][nmodel][p+1] scored on the
+    datasets whose pooled moments are ``gram`` / ``shift`` -> [nprob][nmodel][4] = {n, mse, r2,
+    pooled Pearson IC}, from the moments alone."""
+    import torch
+    nprob, nmodel = int(beta.shape[0]), int(beta.shape[1])
+    out = torch.empty((nprob, nmodel, 4), dtype=torch.float64, device=gram.device)
+    P = _lib.ptr
+    h = _lib.Context.get(gram.device.index).bind_stream()
+    gs, ss = (0, 0) if shared else ((p + 2) * (p + 2), p + 2)
+    _lib.check(_lib.lib().afm_gram_score_f64(h, P(gram), gs, P(shift), ss, p, P(beta), nmodel,
+                                             nprob, P(out)), "afm_gram_score_f64")
+    return out
+
+
+def alpha_grid(G, p: int, eps: float = 1e-3, n_alphas: int = 100) -> np.ndarray:
+    """scikit-learn 1.7.2's ``_alpha_grid`` (l1_ratio = 1, fit_intercept) from a host copy of the
+    pooled Gram ``G`` [p+2][p+2] of [1, x, y]: geomspace(alpha_max, alpha_max * eps, n_alphas)
+    with alpha_max = max |Xc' yc| / n."""
+    n = G[0, 0]
+    q = G[1:p + 1, p + 1] - G[0, 1:p + 1] * G[0, p + 1] / n
+    alpha_max = np.sqrt(q ** 2).max() / n
+    res = np.finfo(np.float64).resolution
+    if alpha_max <= res:
+        return np.full(n_alphas, res)
+    return np.geomspace(alpha_max, alpha_max * eps, num=n_alphas)
+
+
+def _given_alphas(alphas) -> np.ndarray:
+    a = np.sort(np.asarray(alphas, dtype=np.float64).reshape(-1))[::-1].copy()
+    if a.size == 0 or not np.isfinite(a).all() or (a < 0).any():
+        raise ValueError("alphas must be a non-empty list of finite values >= 0")
+    return a
+
+
+def _design(X, y):
+    """-> (Z device [p+1][n] = [x_1..x_p, y], n, p, feature names or None)."""
+    import torch
+    Xc, n, p, names = LinearRegression._as_columns(X)
+    yv = y.to_numpy(dtype=np.float64) if hasattr(y, "to_numpy") else y
+    yt = torch.as_tensor(np.asarray(yv, dtype=np.float64) if not isinstance(yv, torch.Tensor)
+                         else yv, dtype=torch.float64).to(_dev()).reshape(-1)
+    if yt.numel() != n:
+        raise ValueError(f"X has {n} rows, y has {yt.numel()}")
+    if not (torch.isfinite(Xc).all() and torch.isfinite(yt).all()):
+        raise ValueError("Input contains NaN or infinity (as scikit-learn rejects it)")
+    if p > 110:
+        raise ValueError(f"{p} features: the Lasso kernels hold at most 110")
+    return torch.cat([Xc, yt.view(1, -1)], dim=0).contiguous(), n, p, names
+
+
+def _pooled(Z, p: int):
+    """Pooled moments of every row of Z [p+1][n]: segment Grams + Chan pooling."""
+    n = Z.shape[1]
+    nseg = (n + SEG_ROWS - 1) // SEG_ROWS
+    gram, shift = xs_gram(Z, n, SEG_ROWS, SEG_ROWS, list(range(p)), p, nseg=nseg, row_limit=n)
+    return pool_moments(gram, shift, p)
+
+
+def lasso_path(X, y, *, eps: float = 1e-3, n_alphas: int = 100, alphas=None, tol: float = 1e-4,
+               max_iter: int = 1000, positive: bool = False):
+    """Drop-in for ``sklearn.linear_model.lasso_path`` on raw data: X and y are centered
+    internally (no intercept is returned), the grid is scikit-learn's (``alpha_grid``; given
+    alphas are sorted descending), and the whole warm-started path is one
+    ``afm_lasso_batch_f64`` launch on the pooled Gram.  -> (alphas [n_alphas], coefs
+    [p][n_alphas], dual_gaps [n_alphas])."""
+    import torch
+    if tol < 0 or max_iter < 1:
+        raise ValueError("tol must be >= 0 and max_iter >= 1")
+    Z, n, p, _ = _design(X, y)
+    g, s = _pooled(Z, p)
+    a = _given_alphas(alphas) if alphas is not None else alpha_grid(g[0].cpu().numpy(), p, eps,
+                                                                    n_alphas)
+    beta, info = lasso_batch(g, s, p, torch.from_numpy(a).to(Z.device), nprob=1, warm=True,
+                             max_iter=max_iter, tol=tol, positive=positive)
+    return a, beta[0, :, 1:].T.cpu().numpy().copy(), info[0, :, 0].cpu().numpy() / n
+
+
+def _kfold(n: int, k: int):
+    """scikit-learn's unshuffled KFold: contiguous blocks, the first n % k one row longer."""
+    if not 2 <= k <= n:
+        raise ValueError(f"cv={k}: need 2 <= cv <= n_samples = {n}")
+    sizes = np.full(k, n // k, dtype=np.int64)
+    sizes[:n % k] += 1
+    idx, out, a = np.arange(n), [], 0
+    for sz in sizes:
+        out.append((np.concatenate([idx[:a], idx[a + sz:]]), idx[a:a + sz]))
+        a += sz
+    return out
+
+
+class LassoCV:
+    """Drop-in for ``sklearn.linear_model.LassoCV`` (fit_intercept=True, cyclic selection).
+
+    ``cv``: an int (scikit-learn's unshuffled KFold) or an iterable of (train_idx, test_idx) index
+    arrays.  Every fold's train and test moments come from a Gram + Chan pooling over the fold's
+    own rows; all folds walk the alpha grid warm-started in one ``afm_lasso_batch_f64`` launch
+    and are scored from the test moments in one ``afm_gram_score_f64`` launch; ``alpha_``
+    minimises the fold-mean MSE and the refit is a cold ``afm_lasso_fit_f64`` on the full-data
+    Gram.  Results: ``alpha_``, ``alphas_``, ``mse_path_`` [n_alphas][n_folds], ``coef_``,
+    ``intercept_``, ``n_iter_``, ``dual_gap_``, ``n_features_in_``, ``feature_names_in_``."""
+
+    def __init__(self, *, eps: float = 1e-3, n_alphas: int = 100, alphas=None, cv=5,
+                 tol: float = 1e-4, max_iter: int = 1000, positive: bool = False,
+                 fit_intercept: bool = True, selection: str = "cyclic"):
+        if not fit_intercept:
+            raise NotImplementedError("only fit_intercept=True (the reference's usage)")
+        if selection != "cyclic":
+            raise NotImplementedError("only selection='cyclic' (the reference's usage)")
+        if tol < 0 or max_iter < 1 or eps <= 0 or n_alphas < 1:
+            raise ValueError("need tol >= 0, max_iter >= 1, eps > 0 and n_alphas >= 1")
+        self.eps, self.n_alphas = float(eps), int(n_alphas)
+        self.alphas = None if alphas is None else _given_alphas(alphas)
+        self.cv = cv
+        self.tol, self.max_iter, self.positive = float(tol), int(max_iter), bool(positive)
+        self.fit_intercept, self.selection = True, selection
+
+    def fit(self, X, y):
+        import warnings
+
+        import torch
+        Z, n, p, names = _design(X, y)
+        dev = Z.device
+        g, s = _pooled(Z, p)
+        a = self.alphas if self.alphas is not None else alpha_grid(g[0].cpu().numpy(), p,
+                                                                   self.eps, self.n_alphas)
+        folds = _kfold(n, self.cv) if isinstance(self.cv, (int, np.integer)) else \
+            [(np.asarray(tr, dtype=np.int64), np.asarray(te, dtype=np.int64))
+             for tr, te in self.cv]
+        if not folds:
+            raise ValueError("cv yields no split")
+        moments = [[], [], [], []]                      # train gram / shift, test gram / shift
+        for tr, te in folds:
+            if len(tr) == 0 or len(te) == 0 or min(tr.min(), te.min()) < 0 or \
+                    max(tr.max(), te.max()) >= n:
+                raise ValueError("cv: empty fold or row index out of range")
+            for k, rows in ((0, tr), (2, te)):
+                gi, si = _pooled(Z.index_select(1, torch.from_numpy(rows).to(dev)).contiguous(), p)
+                moments[k].append(gi)
+                moments[k + 1].append(si)
+        gtr, str_, gte, ste = (torch.cat(m, dim=0).contiguous() for m in moments)
+        K = len(folds)
+        beta, _ = lasso_batch(gtr, str_, p, torch.from_numpy(a).to(dev), nprob=K, warm=True,
+                              max_iter=self.max_iter, tol=self.tol, positive=self.positive)
+        mse = gram_score(gte, ste, p, beta)[:, :, 1].cpu().numpy()       # [K][n_alphas]
+        best = int(np.argmin(np.mean(mse, axis=0)))
+        self.mse_path_ = np.squeeze(mse.T.copy())          # (a single fold: 1-D, as sklearn)
+        self.alphas_ = a.copy()
+        self.alpha_ = float(a[best])
+        b = torch.empty(p + 1, dtype=torch.float64, device=dev)
+        info = torch.empty(3, dtype=torch.float64, device=dev)
+        h = _lib.Context.get(dev.index).bind_stream()
+        _lib.check(_lib.lib().afm_lasso_fit_f64(h, _lib.ptr(g), _lib.ptr(s), p, self.alpha_,
+                                                self.max_iter, self.tol, int(self.positive),
+                                                _lib.ptr(b), _lib.ptr(info)), "afm_lasso_fit_f64")
+        bh = b.cpu().numpy()
+        gap, tol_y, n_iter = info.cpu().numpy()
+        self.coef_, self.intercept_ = bh[1:].copy(), float(bh[0])
+        self.n_iter_, self.dual_gap_ = int(n_iter), float(gap) / n
+        self.n_features_in_ = p
+        if names is not None:
+            self.feature_names_in_ = names
+        if self.n_iter_ >= self.max_iter and not gap < tol_y:
+            warnings.warn(f"Objective did not converge. Duality gap: {gap:.3e}, tolerance: "
+                          f"{tol_y:.3e}", ConvergenceWarning)
+        self._beta = b
+        return self
+
+    predict = Lasso.predict

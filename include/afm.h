@@ -382,6 +382,34 @@ int afm_zpredict_f64(afm_ctx* ctx, const double* base, int64_t col_stride, int64
  * _set_intercept: mean(y) - mean(x) . w).  info[3] = {gap, tol * y'y, n_iter}. */
 int afm_lasso_fit_f64(afm_ctx* ctx, const double* gram, const double* shift, int p, double alpha,
                       int max_iter, double tol, int positive, double* beta_out, double* info);
+/* Many Lasso fits in one launch -- sklearn's lasso_path / LassoCV solves.  Problem b reads the
+ * pooled (gram + b * gram_stride, shift + b * shift_stride); a stride of 0 shares one Gram among
+ * all problems.  alphas: DEVICE [nalpha], sklearn's alpha (times n on the device, as in
+ * afm_lasso_fit_f64).  beta_out [nprob][nalpha][p+1] = [intercept, w]; info [nprob][nalpha][3] =
+ * {gap, tol * y'y, n_iter}.
+ * warm = 0: nprob * nalpha independent solves from w = 0, one workgroup each; every result is
+ *   afm_lasso_fit_f64's on the same Gram and alpha, bit for bit.
+ * warm = 1: nprob workgroups, each walking its problem's alphas in the order given, every solve
+ *   started from the previous one's weights (the warm start of sklearn's paths) with H = Q w
+ *   recomputed: H[j] = sum_k Q[j][k] w[k], k ascending, a multiply then an add.
+ * A workgroup holds p * 128 doubles of LDS (one per compute unit at p = 110); the workgroups are
+ * independent, so a grid larger than the chip runs in rounds.  1 <= p <= 110. */
+int afm_lasso_batch_f64(afm_ctx* ctx, const double* gram, int64_t gram_stride, const double* shift,
+                        int64_t shift_stride, int p, const double* alphas, int nalpha,
+                        int64_t nprob, int warm, int max_iter, double tol, int positive,
+                        double* beta_out, double* info);
+/* Scores of linear models on a dataset known by its pooled moments alone (no pass over rows):
+ * dataset b = (gram + b * gram_stride, shift + b * shift_stride) of [1, x, y], model (b, i) =
+ * beta[b][i][p+1] = [intercept, w]; out [nprob][nmodel][4] = {n, mse, r2, ic}.  With the means m,
+ * ybar and the centered Q, q, yy of the dataset: d = (ybar - b0) - m.w, SSE = ((yy - 2 w.q) +
+ * w'Qw) + n d d, mse = SSE / n, r2 = 1 - SSE / yy (sklearn's score), ic = w.q / sqrt(w'Qw yy) (the
+ * pooled Pearson correlation of prediction and y, np.corrcoef; NaN when w'Qw == 0).  One wave
+ * per model; every sum sequential in feature order, multiply then add: (Qw)[j] = sum_k w[k]
+ * Q[k][j] over k ascending (zero weights skipped), then w.q, w'Qw = sum_j w[j] (Qw)[j] and m.w
+ * over j ascending.  1 <= p <= 110. */
+int afm_gram_score_f64(afm_ctx* ctx, const double* gram, int64_t gram_stride, const double* shift,
+                       int64_t shift_stride, int p, const double* beta, int nmodel, int64_t nprob,
+                       double* out);
 
 #ifdef __cplusplus
 }
