@@ -720,9 +720,15 @@ __global__ __launch_bounds__(kThreads) void ols_solve_kernel(SolveArgs s) {
     for (int j = tid; j <= q; j += kThreads) mean[j] = (j == 0) ? 1.0 : G[gx[j]] / n;   // shifted
     for (int r = tid; r < q; r += kThreads) {
         const int gr = gx[r + 1];
-        const double d = G[gr * p2 + gr] - G[gr] * G[gr] / n;
-        dsc[r] = r < p ? (d > 0 ? 1.0 / __builtin_sqrt(d) : 0.0) : 1.0;
-        if (r < p) drop[r] = !(d > 0);
+        const double g2 = G[gr * p2 + gr];
+        const double d = g2 - G[gr] * G[gr] / n;
+        // no resolvable variance: d is at most the rounding error of forming it from an n-term
+        // sum of squares and an n-term sum, (n + 3) 2^-53 G[r][r] in any summation order.  With
+        // shifted moments a constant column gives exactly 0; with raw moments it gives noise of
+        // either sign, which 1 / sqrt(d) would rescale to a unit pivot.
+        const bool keep = d > (n + 3.0) * 0x1p-53 * g2;
+        dsc[r] = r < p ? (keep ? 1.0 / __builtin_sqrt(d) : 0.0) : 1.0;
+        if (r < p) drop[r] = !keep;
     }
     __syncthreads();
     // lower triangle of D C D (packed rows)

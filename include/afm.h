@@ -148,7 +148,13 @@ int afm_xs_gram_f64(afm_ctx* ctx, const double* base, int64_t col_stride, int64_
                     const uint64_t* bits, int64_t seg0, int64_t nseg, double* gram, double* shift);
 /* OLS with intercept per segment from (gram, shift): beta[s] = [intercept, b_1..b_p].  Scaled
  * (unit-diagonal) Cholesky of the centered normal equations; a regressor whose pivot falls below
- * tol is dropped (b = 0) -- rank[s] counts the kept ones.  Segments with n <= p get NaN. */
+ * tol is dropped (b = 0) -- rank[s] counts the kept ones.  Segments with n <= p get NaN.
+ * A regressor with no resolvable variance is dropped before the factorisation: one whose centered
+ * sum of squares d = G[r][r] - G[0][r]^2 / n is not above (n + 3) 2^-53 G[r][r], the worst-case
+ * rounding error of forming d from an n-term sum of squares and an n-term sum (G[r][r] as stored
+ * in the representation passed).  A constant column gives exactly 0 under a shift and rounding
+ * noise of either sign in raw moments (shift = 0, afm_gram_tree_f64's final output); both are
+ * dropped.  Raw moments also cost a kept column (mean / sd)^2 * 2^-53 of relative accuracy. */
 int afm_ols_solve_f64(afm_ctx* ctx, const double* gram, const double* shift, int p, int64_t nseg,
                       double tol, double* beta, double* nobs, int32_t* rank);
 /* Exact (Chan) combination of nseg per-segment moments into one (gram, shift) -- the pooled OLS
