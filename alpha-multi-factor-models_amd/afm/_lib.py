@@ -6,6 +6,7 @@ the library in-tree.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import threading
@@ -159,6 +160,18 @@ class Context:
         s = torch.cuda.current_stream(self.device).cuda_stream
         check(lib().afm_ctx_set_stream(self.handle, P(s)), "afm_ctx_set_stream")
         return self.handle
+
+    @contextlib.contextmanager
+    def on(self, stream):
+        """``with ctx.on(stream) as h:`` -- the block's launches go to ``stream``: torch's current
+        stream and this context are switched together, and on the way out (also when the block
+        raises) the context is bound again to the stream that is current once more."""
+        import torch
+        try:
+            with torch.cuda.stream(stream):
+                yield self.bind_stream()
+        finally:
+            self.bind_stream()
 
 
 def ptr(t) -> P:

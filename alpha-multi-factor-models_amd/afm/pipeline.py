@@ -175,7 +175,8 @@ def _round_up(x: int, m: int = 64) -> int:
     return (x + m - 1) // m * m
 
 
-def _even(n: int, world: int, rank: int):
+def even_range(n: int, world: int, rank: int):
+    """[lo, hi) of ``rank``'s share of ``n`` items split evenly over ``world`` ranks."""
     return n * rank // world, n * (rank + 1) // world
 
 
@@ -197,33 +198,44 @@ class Pipeline:
     one all-gather of the test-date predictions and row bits, one all_to_all of per-date FM
     partials to the date owners (+ an all-gather of the betas), one all-gather of the rebalance
     results (rebalance dates are split over ranks).  Every sum follows the same fixed trees as
-    one device, so every result is bit-identical to N = 1."""
+    one device, so every result is bit-identical to N = 1.
+
+    Streams: a step runs on ``main``, side work forked onto ``side`` / ``side2`` / ``side3``.  Every
+    switch of stream is a ``with self.ctx.on(stream) as h:`` scope (torch's current stream and the
+    afm context move and are restored together); a helper that launches takes the scope's ``h``."""
 
     def __init__(self, grid: PanelGrid, cfg: PipelineConfig | None = None, comm=None):
         import torch
         self.full = grid
         self.comm = comm
-        W = comm.world if comm is not None else 1
-        rk = comm.rank if comm is not None else 0
-        self.W, self.rank = W, rk
+        self.W = W = comm.world if comm is not None else 1
+        self.rank = comm.rank if comm is not None else 0
         self.cfg = c = cfg or PipelineConfig()
-        dev = grid.device
         T, lda, A = grid.T, grid.lda, grid.A
-        nch = (T + 63) // 64
-        self.T, self.lda, self.A, self.nch = T, lda, A, nch
-        self.sp = sp = Split.of(grid.dates, c.train_end, c.valid_end)
+        self.T, self.lda, self.A, self.nch = T, lda, A, (T + 63) // 64
+        self.sp = Split.of(grid.dates, c.train_end, c.valid_end)
         self.features = list(c.features) if c.features is not None else FEATURES
-        self.p = p = len(self.features)
-        self.p2 = p + 2
-        self.pf = len(c.fm_features)
-        f64 = dict(dtype=torch.float64, device=dev)
-        i64 = dict(dtype=torch.int64, device=dev)
-        i32 = dict(dtype=torch.int32, device=dev)
-        L = _lib.lib()
-        # ---- asset shard: whole blocks of the fixed split ----
+        self.p, self.pf = len(self.features), len(c.fm_features)
+        self.p2 = self.p + 2
+        self.fwd_early = bool(c.analyzer and c.early_fwd)
+        self.fm_at = c.fm_fork if W == 1 else "gram"     # N > 1: beside the lasso, always
+        # tensor options (f64, i64, i32) on the panel's device
+        self._opts = tuple(dict(dtype=t, device=grid.device)
+                           for t in (torch.float64, torch.int64, torch.int32))
+        self._init_shard()
+        self._init_shard_buffers()
+        self._init_fm_buffers()
+        self._init_reb_buffers()
+        self._init_analyzer_buffers()
+        self._init_streams()
+        self._init_slabs()
+
+    def _init_shard(self):
+        """The asset shard: whole blocks of the fixed split, and this rank's slice of the grid."""
+        import torch
+        grid, W, rk, A, lda = self.full, self.W, self.rank, self.A, self.lda
         if N_BLOCKS % W:
             raise ValueError(f"{W} ranks: the GPU count must divide {N_BLOCKS}")
-        self.nblk = N_BLOCKS
         self.blk = blk = block_assets(lda)
         self.rb_per_blk = blk // 64
         if self.rb_per_blk > 32:          # afm_gram_tree_f64 merges at most 32 leaves a level
@@ -231,28 +243,27 @@ class Pipeline:
                              f"{N_BLOCKS * 32 * 64} assets ({N_BLOCKS} blocks x 32 row-blocks "
                              f"of 64)")
         self.nblk_r = N_BLOCKS // W
-        self.ranges = []
-        for q in range(W):
-            lo = min(q * self.nblk_r * blk, A)
-            self.ranges.append((lo, min((q + 1) * self.nblk_r * blk, A)))
+        self.wide = wide = self.nblk_r * blk           # padded shard width of the exchanges
+        self.ranges = [(min(q * wide, A), min((q + 1) * wide, A)) for q in range(W)]
         a0, a1 = self.ranges[rk]
         self.a0, self.A_r = a0, a1 - a0
         self.lda_r = lda_r = _round_up(max(self.A_r, 1))
-        self.wide = self.nblk_r * blk                  # padded shard width of the exchanges
+        self.nrb = (self.A_r + 63) // 64               # this shard's 64-asset row-blocks
         if W == 1:
             self.g = grid
         else:
             sl = slice(a0, a0 + lda_r)
+            planes = ("close", "volume", "ret1d", "excess", "valid", "vbits")
             self.g = PanelGrid(dates=grid.dates, ids=grid.ids[a0:a1],
-                               close=grid.close[:, sl].contiguous(),
-                               volume=grid.volume[:, sl].contiguous(),
-                               ret1d=grid.ret1d[:, sl].contiguous(),
-                               excess=grid.excess[:, sl].contiguous(),
-                               valid=grid.valid[:, sl].contiguous(),
-                               vbits=grid.vbits[:, sl].contiguous())
+                               **{k: getattr(grid, k)[:, sl].contiguous() for k in planes})
         self.feat = torch.as_tensor(np.array([COL[n] for n in self.features], np.int32),
-                                    device=dev)
-        # ---- local (shard) buffers ----
+                                    device=grid.device)
+
+    def _init_shard_buffers(self):
+        """The shard's panel, row sets, z statistics, pooled-Gram partials and the fit."""
+        import torch
+        f64, i64, i32 = self._opts
+        T, nch, lda_r, p, W, nrb = self.T, self.nch, self.lda_r, self.p, self.W, max(self.nrb, 1)
         self.out = torch.full((N_FACTORS, T, lda_r), float("nan"), **f64)
         self.nanfree = torch.zeros((nch, lda_r), **i64)
         self.finite = torch.zeros((nch, lda_r), **i64)
@@ -263,11 +274,10 @@ class Pipeline:
         self.sd = torch.empty((p, lda_r), **f64)
         self.zs = torch.empty((p + 1, lda_r, 2), **f64)
         self.asset_ok = torch.empty(lda_r, **i32)
-        self.nrb = (self.A_r + 63) // 64                 # this shard's 64-asset row-blocks
-        self.pe = pe = L.afm_zgram_part_bytes(p) // 8
-        self.pool_part = torch.empty((max(self.nrb, 1), N_CHUNKS, pe), **f64)
-        self.pool_c1 = torch.empty((max(self.nrb, 1) * (N_CHUNKS // CHUNK_TREE[0]), pe), **f64)
-        self.pool_rb = torch.empty((max(self.nrb, 1), pe), **f64)
+        self.pe = pe = _lib.lib().afm_zgram_part_bytes(p) // 8
+        self.pool_part = torch.empty((nrb, N_CHUNKS, pe), **f64)
+        self.pool_c1 = torch.empty((nrb * (N_CHUNKS // CHUNK_TREE[0]), pe), **f64)
+        self.pool_rb = torch.empty((nrb, pe), **f64)
         self.pool_blk = torch.zeros((self.nblk_r + 1, pe), **f64)   # + the train_end subtree
         self.pool_all = torch.zeros((N_BLOCKS, pe), **f64)
         self.te_part = torch.zeros((self.nblk_r, pe), **f64)
@@ -277,32 +287,44 @@ class Pipeline:
         self.te_gram = torch.zeros((1, self.p2, self.p2), **f64)
         self.lasso_beta = torch.empty(p + 1, **f64)
         self.lasso_info = torch.empty(3, **f64)
-        # FM design: [1, FM30 factor values, target] per date
-        self.fm_cols = torch.as_tensor(np.array([COL[n] for n in c.fm_features], np.int32),
-                                       device=dev)
-        self.pef = pef = L.afm_zgram_part_bytes(self.pf) // 8
+
+    def _init_fm_buffers(self):
+        """FM design: [1, FM30 factor values, target] per date; the dates split over the ranks."""
+        import torch
+        f64, _, i32 = self._opts
+        T, W, pf = self.T, self.W, self.pf
+        self.fm_cols = torch.as_tensor(np.array([COL[n] for n in self.cfg.fm_features], np.int32),
+                                       device=self.full.device)
+        self.pef = pef = _lib.lib().afm_zgram_part_bytes(pf) // 8
         self.fm_part = torch.zeros((T, self.nblk_r, pef), **f64)
         self.fm_sub = torch.zeros((T, pef), **f64)      # this shard's subtree per date
-        self.fdr = [_even(T, W, q) for q in range(W)]   # FM dates owned by each rank
-        fd0, fd1 = self.fdr[rk]
+        self.fdr = [even_range(T, W, q) for q in range(W)]   # FM dates owned by each rank
+        fd0, fd1 = self.fdr[self.rank]
         self.fd0, self.fnd = fd0, fd1 - fd0
         self.fnd_max = max(b - a for a, b in self.fdr)
-        self.fm_gram = torch.empty((max(self.fnd, 1), self.pf + 2, self.pf + 2), **f64)
-        self.fm_shift = torch.zeros((max(self.fnd, 1), self.pf + 2), **f64)
-        self.fm_beta_own = torch.full((self.fnd_max, self.pf + 1), float("nan"), **f64)
+        self.fm_gram = torch.empty((max(self.fnd, 1), pf + 2, pf + 2), **f64)
+        self.fm_shift = torch.zeros((max(self.fnd, 1), pf + 2), **f64)
+        self.fm_beta_own = torch.full((self.fnd_max, pf + 1), float("nan"), **f64)
         self.fm_nobs_own = torch.zeros(self.fnd_max, **f64)
         self.fm_rank_own = torch.zeros(self.fnd_max, **i32)
         if W == 1:
             self.fm_beta, self.fm_nobs, self.fm_rank = (self.fm_beta_own, self.fm_nobs_own,
                                                         self.fm_rank_own)
         else:
-            self.fm_beta = torch.empty((T, self.pf + 1), **f64)
+            self.fm_beta = torch.empty((T, pf + 1), **f64)
             self.fm_nobs = torch.empty(T, **f64)
             self.fm_rank = torch.empty(T, **i32)
-        self.fm_mean = torch.empty(self.pf + 1, **f64)
-        self.fm_t = torch.empty(self.pf + 1, **f64)
-        self.pred_r = torch.full((T, lda_r), float("nan"), **f64)
-        # ---- full-width planes the rebalance / analyzer read ----
+        self.fm_mean = torch.empty(pf + 1, **f64)
+        self.fm_t = torch.empty(pf + 1, **f64)
+
+    def _init_reb_buffers(self):
+        """The predictions, the full-width planes the rebalance / analyzer read, the rebalance
+        dates (split over the ranks) with their books, and the PnL series."""
+        import torch
+        f64, i64, i32 = self._opts
+        grid, c, sp, W, rk = self.full, self.cfg, self.sp, self.W, self.rank
+        T, lda, nch, dev = self.T, self.lda, self.nch, self.full.device
+        self.pred_r = torch.full((T, self.lda_r), float("nan"), **f64)
         if W == 1:
             self.pred, self.zrows_full, self.alldf_full = self.pred_r, self.zrows, self.alldf
             self.target, self.tmr = self.out[TARGET], self.out[TMR]
@@ -312,8 +334,7 @@ class Pipeline:
             self.alldf_full = torch.zeros((nch, lda), **i64)
             self.target = torch.full((T, lda), float("nan"), **f64)
             self.tmr = torch.full((T, lda), float("nan"), **f64)
-            win = c.window if c.window is not None else T
-            self.lab0 = 0 if c.window is None else max(0, sp.s0 - int(win) - 1)
+            self.lab0 = 0 if c.window is None else max(0, sp.s0 - int(c.window) - 1)
         # rebalance dates: the test dates that can carry predictions (a present observation that
         # is not the asset's last -- every other row lacks the target)
         vb = grid.valid.cpu().numpy()
@@ -337,62 +358,62 @@ class Pipeline:
         # adjacent dates' prediction sets)
         self.reb_split = W > 1 and c.reb_split
         Wr = W if self.reb_split else 1
-        self.rrange = [_even(nd, Wr, q) for q in range(Wr)]
-        i0, i1 = self.rrange[rk if self.reb_split else 0]
-        self.i0, self.i1 = i0, i1
+        self.rrange = [even_range(nd, Wr, q) for q in range(Wr)]
+        self.i0, self.i1 = i0, i1 = self.rrange[rk if self.reb_split else 0]
         self.e0, self.e1 = (max(i0 - 1, 0), min(i1 + 1, nd)) if self.reb_split else (0, nd)
         self.rd_ext = torch.from_numpy(rd[self.e0:self.e1].copy()).to(dev)
         self.rdates = torch.from_numpy(rd).to(dev)
         self.reb_ext = reb_buffers(self.e1 - self.e0) if self.reb_split else self.reb
-        self.nr_max = max(b - a for a, b in self.rrange)
-        self._reb_rows = self._fm_rows = self._an_rows = None
+        self._rows = {}                     # cached row indices of the share gathers (N > 1)
         self._send = {}                     # packed send buffers of the exchanges (N > 1)
         self.pnl = {"value": torch.empty(nd + 1, **f64), "turnover": torch.empty(nd, **f64),
                     "long_ret": torch.empty(nd, **f64), "short_ret": torch.empty(nd, **f64)}
-        # analyzer on the test sub-grid (64-date aligned, so the bit words line up)
+
+    def _init_analyzer_buffers(self):
+        """The analyzer on the test sub-grid (64-date aligned, so the bit words line up)."""
+        import torch
+        f64, i64, i32 = self._opts
+        grid, sp, W, T, lda, dev = self.full, self.sp, self.W, self.T, self.lda, self.full.device
         self.an_a0 = (sp.s0 // 64) * 64
-        Ta = T - self.an_a0
-        self.Ta = Ta
-        self.price_bits = torch.zeros((nch, lda), **i64)  # df_test rows (all_df, date >= valid_end)
-        if c.analyzer:
-            self.an = {
-                "fr": torch.empty((3, Ta, lda), **f64),
-                "scratch": torch.empty((Ta, lda), **f64),
-                "rows": torch.empty((4, Ta, lda), **f64),
-                "rows_idx": torch.empty((Ta, lda), **i32),
-                "nrows": torch.empty(Ta, **i32),
-                "skey": torch.empty((Ta, lda), **i64),
-                "sidx": torch.empty((Ta, lda), **i32),
-                "ra": torch.empty((Ta, lda), **i32),
-                "rd": torch.empty((Ta, lda), **i32),
-            }
-            ad = np.arange(sp.s0 - self.an_a0, Ta, dtype=np.int32)   # test dates, sub-grid index
-            self.an_dates = torch.from_numpy(ad).to(dev)
-            self.an_nd = nad = len(ad)
-            # N > 1: each rank evaluates an even share of the test dates (every stage of the
-            # analyzer but the final series is per date); one packed all-gather of the per-date
-            # results, then every rank runs the series
-            self.an_rng = _even(nad, W, rk) if W > 1 else (0, nad)
-            self.an_nmax = max(b - a for a, b in (_even(nad, W, q) for q in range(W)))
-            years = np.asarray(grid.dates).astype("datetime64[Y]").astype(np.int64) + 1970
-            yr = years[self.an_a0 + ad].astype(np.int32)
-            self.an_year0, self.an_nyears = int(yr.min()), int(yr.max() - yr.min() + 1)
-            self.an_year = torch.from_numpy(yr).to(dev)
-            self.an.update({
-                "ic": torch.empty((nad, 3), **f64),
-                "layer_mean": torch.empty((nad, 3, 10), **f64),
-                "layer_cnt": torch.empty((nad, 10), **i32),
-                "port": torch.empty((nad, 3), **f64),
-                "cum_layer": torch.empty((nad, 3, 10), **f64),
-                "ls": torch.empty((nad, 3, 5), **f64),
-                "cum_port": torch.empty((nad, 3), **f64),
-                "ir": torch.empty((self.an_nyears, 3), **f64),
-                "ir_scratch": torch.empty((3 * self.an_nyears, nad), **f64),
-            })
+        self.Ta = Ta = T - self.an_a0
+        self.price_bits = torch.zeros((self.nch, lda), **i64)   # df_test rows (all_df, test dates)
+        if not self.cfg.analyzer:
+            return
+        ad = np.arange(sp.s0 - self.an_a0, Ta, dtype=np.int32)   # test dates, sub-grid index
+        self.an_dates = torch.from_numpy(ad).to(dev)
+        self.an_nd = nad = len(ad)
+        years = np.asarray(grid.dates).astype("datetime64[Y]").astype(np.int64) + 1970
+        yr = years[self.an_a0 + ad].astype(np.int32)
+        self.an_year0, self.an_nyears = int(yr.min()), int(yr.max() - yr.min() + 1)
+        self.an_year = torch.from_numpy(yr).to(dev)
+        self.an = {
+            "fr": torch.empty((3, Ta, lda), **f64), "scratch": torch.empty((Ta, lda), **f64),
+            "rows": torch.empty((4, Ta, lda), **f64), "rows_idx": torch.empty((Ta, lda), **i32),
+            "nrows": torch.empty(Ta, **i32), "skey": torch.empty((Ta, lda), **i64),
+            "sidx": torch.empty((Ta, lda), **i32), "ra": torch.empty((Ta, lda), **i32),
+            "rd": torch.empty((Ta, lda), **i32), "ic": torch.empty((nad, 3), **f64),
+            "layer_mean": torch.empty((nad, 3, 10), **f64),
+            "layer_cnt": torch.empty((nad, 10), **i32), "port": torch.empty((nad, 3), **f64),
+            "cum_layer": torch.empty((nad, 3, 10), **f64), "ls": torch.empty((nad, 3, 5), **f64),
+            "cum_port": torch.empty((nad, 3), **f64),
+            "ir": torch.empty((self.an_nyears, 3), **f64),
+            "ir_scratch": torch.empty((3 * self.an_nyears, nad), **f64),
+        }
+        # N > 1: each rank evaluates an even share of the test dates (every stage of the
+        # analyzer but the final series is per date); one packed all-gather of the per-date
+        # results, then every rank runs the series
+        self.an_ranges = [even_range(nad, W, q) for q in range(W)]
+        self.an_rng = self.an_ranges[self.rank]
+
+    def _init_streams(self):
+        """The afm context and the step's streams, created in the order main, side, side2, side3."""
+        import torch
+        c, W, dev = self.cfg, self.W, self.full.device
         self.ctx = _lib.Context.get(dev.index)
         if c.fm_fork not in ("gram", "predict", "analyzer", "rebalance"):
             raise ValueError(f"fm_fork={c.fm_fork!r}: expected gram, predict, analyzer or "
                              "rebalance")
+        self.ncu = torch.cuda.get_device_properties(dev).multi_processor_count
         self.main = torch.cuda.Stream(device=dev, priority=-8 if c.main_priority else 0)
         self.fm_grid = c.fm_grid          # the FM Grams' persistent grid (0: one per CU)
         if c.fm_free_cus > 0:
@@ -400,7 +421,7 @@ class Pipeline:
             self.side = self._side_owner.stream
             # one workgroup per CU the masked stream may use: a full-width grid would run the
             # surplus workgroups in a second round
-            self.fm_grid = torch.cuda.get_device_properties(dev).multi_processor_count - c.fm_free_cus
+            self.fm_grid = self.ncu - c.fm_free_cus
         else:
             self.side = torch.cuda.Stream(device=dev, priority=0)
         self.side2 = torch.cuda.Stream(device=dev, priority=0)
@@ -412,32 +433,33 @@ class Pipeline:
                       if W > 1 else self.main)
         self.streams = (self.main, self.side, self.side2) + ((self.side3,) if W > 1 else ())
         self.labels_done = torch.cuda.Event()
-        self.fwd_early = False
+
+    def _init_slabs(self):
+        """The time slabs of the streamed / early factor stages: bounds, carried state, events."""
+        import torch
+        f64, i64, _ = self._opts
+        L, c, sp, T, A_r, lda_r = _lib.lib(), self.cfg, self.sp, self.T, self.A_r, self.lda_r
         # early z statistics: the first slab ends at the first 64-date boundary past the train
         # window (the slab API's alignment)
         self.ta = min(((sp.tr1 + 63) // 64) * 64, T)
         nslab = c.zstats_slabs
         if nslab < 0:
-            ncu = torch.cuda.get_device_properties(dev).multi_processor_count
-            nslab = 6 if ((self.A_r + 63) // 64) * 10 <= ncu else 0
-        self.stream_z = nslab >= 2 and self.A_r > 0 and sp.tr1 > 0 and T >= 128
+            nslab = 6 if self.nrb * 10 <= self.ncu else 0
+        self.stream_z = nslab >= 2 and A_r > 0 and sp.tr1 > 0 and T >= 128
         if self.stream_z:
-            bounds = sorted({0, T} | {min(T, ((i * T // nslab + 63) // 64) * 64)
-                                      for i in range(1, nslab)})
-            self.zbounds = bounds
-            self.zstate = torch.empty((5, p, lda_r), **f64)
-            self.zparts = [torch.empty(int(L.afm_factors_part_words(self.ctx.handle, self.A_r,
-                                                                    lda_r, a, z)), **i64)
+            self.zbounds = bounds = sorted({0, T} | {min(T, ((i * T // nslab + 63) // 64) * 64)
+                                                     for i in range(1, nslab)})
+            self.zstate = torch.empty((5, self.p, lda_r), **f64)
+            self.zparts = [torch.empty(int(L.afm_factors_part_words(self.ctx.handle, A_r, lda_r,
+                                                                    a, z)), **i64)
                            for a, z in zip(bounds[:-1], bounds[1:])]
             self.zslab_done = [torch.cuda.Event() for _ in bounds[:-1]]
-            self.zstats_done = torch.cuda.Event()
-        self.early = (bool(c.early_zstats) and not self.stream_z and self.A_r > 0 and self.ta < T)
+        self.early = (bool(c.early_zstats) and not self.stream_z and A_r > 0 and self.ta < T)
         if self.early or self.stream_z:
-            nb = int(L.afm_factors_state_bytes(self.ctx.handle, self.A_r))
+            nb = int(L.afm_factors_state_bytes(self.ctx.handle, A_r))
             self.fstate = torch.empty(nb // 8 + 1, **f64)
             self.slab1_done = torch.cuda.Event()
-            if not self.stream_z:
-                self.zstats_done = torch.cuda.Event()
+            self.zstats_done = torch.cuda.Event()
 
     @property
     def labels_in_factor_stage(self) -> bool:
@@ -449,30 +471,70 @@ class Pipeline:
     def n_asset_days_local(self) -> int:
         return int(self.g.valid.sum().item())
 
-    # ------------------------------------------------------------------------------------------
-    def _pooled_blocks(self, h, t0, nt, mark=None):
+    # ---- launch runs shared by the stages ------------------------------------------------------
+    def _labels(self, stream, full=False):
+        """The two label planes on ``stream``, then ``labels_done``: this shard's planes of the
+        panel, or (``full``, N > 1) the full-width planes the rebalance reads."""
+        g, lda, t0, tgt, tmr = ((self.full, self.lda, self.lab0, self.target, self.tmr) if full
+                                else (self.g, self.lda_r, 0, self.out[TARGET], self.out[TMR]))
+        P = _lib.ptr
+        with self.ctx.on(stream) as h:
+            _lib.check(_lib.lib().afm_labels_f64(h, self.T, lda, t0, self.T, P(g.excess),
+                                                 P(g.ret1d), P(g.vbits), P(tgt), P(tmr)), "labels")
+            self.labels_done.record(stream)
+
+    def _last_obs_rows(self, h, t0=None, t1=None):
+        """nanfree -> all_df rows and finite -> frows (an asset's last observation dropped), of
+        every date or of the dates [t0, t1)."""
+        L, P = _lib.lib(), _lib.ptr
+        fn, rng = ((L.afm_drop_last_obs_bits, ()) if t0 is None
+                   else (L.afm_drop_last_obs_bits_range, (t0, t1)))
+        for src, dst in ((self.nanfree, self.alldf), (self.finite, self.frows)):
+            _lib.check(fn(h, self.T, self.lda_r, P(self.g.vbits), P(src), P(dst), *rng),
+                       "last-obs rows")
+
+    def _zrows(self, h, w0, nw, nt):
+        """The z-score rows (frows of the surviving assets) of the ``nw`` 64-date words from
+        ``w0`` on, ``nt`` dates."""
+        P = _lib.ptr
+        _lib.check(_lib.lib().afm_row_bits(h, nw, self.lda_r, P(self.frows[w0:]), None,
+                                           P(self.asset_ok), 0, nt, P(self.zrows[w0:])), "z rows")
+
+    def _zstats(self, h, nw, nt):
+        """The train window's z statistics, the surviving assets, and the z-score rows of the
+        first ``nw`` words (``nt`` dates)."""
+        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
+        T, lda_r, p = self.T, self.lda_r, self.p
+        chk(L.afm_zscore_stats_f64(h, P(self.out), T * lda_r, T, lda_r, P(self.feat), p,
+                                   P(self.alldf), 0, self.sp.tr1, P(self.mu), P(self.sd)),
+            "zscore stats")
+        chk(L.afm_zstats_finalize_f64(h, P(self.mu), P(self.sd), p, lda_r, P(self.zs),
+                                      P(self.asset_ok)), "zstats finalize")
+        self._zrows(h, 0, nw, nt)
+
+    def _pooled_blocks(self, h, t0, nt, bufs=None, mark=None):
         """This shard's pooled-Gram block results (rows of the dates [t0, t0 + nt)): row-block x
         chunk partials, then the tree -- the chunks of a row-block (32, then 2), the row-blocks
-        of an asset block -> pool_blk[0:nblk_r]."""
+        of an asset block -> pool_blk[0:nblk_r], or in the buffers ``bufs`` (part, c1, rb, blk)
+        instead of the step's."""
         L, P, chk = _lib.lib(), _lib.ptr, _lib.check
         T, lda, p = self.T, self.lda_r, self.p
-        self.pool_blk.zero_()
+        part, c1b, rb, blk = bufs or (self.pool_part, self.pool_c1, self.pool_rb, self.pool_blk)
+        blk.zero_()
         if self.nrb == 0:
             return
         if mark is not None:
             mark("k_gram", 0)
         chk(L.afm_zpool_f64(h, P(self.out), T * lda, lda, P(self.feat), None, p, TARGET,
                             P(self.zs), p, P(self.zrows), t0, nt, 0, self.nrb, self.A_r,
-                            N_CHUNKS, P(self.pool_part), 0), "zpool")
+                            N_CHUNKS, P(part), 0), "zpool")
         if mark is not None:
             mark("k_gram", 1)
         c1, c2 = CHUNK_TREE
-        chk(L.afm_gram_tree_f64(h, p, P(self.pool_part), self.nrb * N_CHUNKS, c1, 0,
-                                P(self.pool_c1)), "tree chunks")
-        chk(L.afm_gram_tree_f64(h, p, P(self.pool_c1), self.nrb * c2, c2, 0, P(self.pool_rb)),
-            "tree chunks 2")
-        chk(L.afm_gram_tree_f64(h, p, P(self.pool_rb), self.nrb, self.rb_per_blk, 0,
-                                P(self.pool_blk)), "tree row-blocks")
+        chk(L.afm_gram_tree_f64(h, p, P(part), self.nrb * N_CHUNKS, c1, 0, P(c1b)), "tree chunks")
+        chk(L.afm_gram_tree_f64(h, p, P(c1b), self.nrb * c2, c2, 0, P(rb)), "tree chunks 2")
+        chk(L.afm_gram_tree_f64(h, p, P(rb), self.nrb, self.rb_per_blk, 0, P(blk)),
+            "tree row-blocks")
 
     def _te_subtree(self, h, t):
         """This shard's subtree of the train_end date's Gram -> pool_blk[nblk_r]."""
@@ -500,16 +562,38 @@ class Pipeline:
                                 P(self.fm_sub)), "tree fm blocks")
 
     def _fm_solve(self, h, sub):
-        """Owned dates: the rank subtrees ``sub`` [fnd][W][part] -> Grams, solves; every rank then
-        gets every date's betas and the FM statistics."""
+        """Owned dates: the rank subtrees ``sub`` [fnd][W][part] -> Grams, solves."""
         L, P, chk = _lib.lib(), _lib.ptr, _lib.check
-        c, pf, T = self.cfg, self.pf, self.T
+        pf = self.pf
         if self.fnd > 0:
             chk(L.afm_gram_tree_f64(h, pf, P(sub), self.fnd * self.W, self.W, 1,
                                     P(self.fm_gram)), "tree fm ranks")
-            chk(L.afm_ols_solve_f64(h, P(self.fm_gram), P(self.fm_shift), pf, self.fnd, c.tol,
-                                    P(self.fm_beta_own), P(self.fm_nobs_own),
+            chk(L.afm_ols_solve_f64(h, P(self.fm_gram), P(self.fm_shift), pf, self.fnd,
+                                    self.cfg.tol, P(self.fm_beta_own), P(self.fm_nobs_own),
                                     P(self.fm_rank_own)), "fm solve")
+
+    def _fm_stats(self, h):
+        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
+        chk(L.afm_fama_macbeth_f64(h, P(self.fm_beta), P(self.fm_rank), self.T, self.pf + 1,
+                                   P(self.fm_mean), P(self.fm_t)), "fama_macbeth")
+
+    # ---- the factor stage's three paths --------------------------------------------------------
+    def _factors_one_pass(self, h, lab_side, mark):
+        """The factor panel in one call on the main stream, then the all_df rows.  One GPU: the
+        two label planes on the second side stream, enqueued after the factor kernel (it runs
+        on the CUs the factor workgroups leave free); the z statistics wait for them."""
+        L, P, g = _lib.lib(), _lib.ptr, self.g
+        if self.A_r > 0:
+            mark("k_factor", 0)
+            _lib.check(L.afm_factors_f64(h, self.T, self.A_r, self.lda_r, P(g.close), P(g.volume),
+                                         None if lab_side else P(g.ret1d),
+                                         None if lab_side else P(g.excess), P(g.vbits),
+                                         P(self.out), P(self.nanfree), P(self.finite)), "factors")
+            mark("k_factor", 1)
+            if lab_side:
+                self._labels(self.side2)
+            self._last_obs_rows(h)
+        mark("factors", 1)
 
     def _factors_streamed(self, h, lab_side, mark):
         """The factor panel in time slabs (zbounds) on the main stream, each slab's all_df rows
@@ -521,15 +605,9 @@ class Pipeline:
         slab, inside the factors stage)."""
         import torch
         L, P, chk = _lib.lib(), _lib.ptr, _lib.check
-        g, sp, T, lda_r, p, A_r = self.g, self.sp, self.T, self.lda_r, self.p, self.A_r
-        lab_stream = self.side2 if lab_side else self.main
-        with torch.cuda.stream(lab_stream):
-            h2 = self.ctx.bind_stream()
-            chk(L.afm_labels_f64(h2, T, lda_r, 0, T, P(g.excess), P(g.ret1d), P(g.vbits),
-                                 P(self.out[TARGET]), P(self.out[TMR])), "labels")
-            self.labels_done.record(lab_stream)
-        h = self.ctx.bind_stream()
-        b, tr1 = self.zbounds, sp.tr1
+        g, T, lda_r, p, A_r = self.g, self.T, self.lda_r, self.p, self.A_r
+        self._labels(self.side2 if lab_side else self.main)
+        b, tr1 = self.zbounds, self.sp.tr1
         for i in range(len(b) - 1):
             t0, t1 = b[i], b[i + 1]
             # the slab on the main stream; its row masks, all_df rows and z statistics on the side
@@ -542,14 +620,11 @@ class Pipeline:
                                              P(g.vbits), P(self.out), P(self.fstate), P(part)),
                 "factors slab")
             self.zslab_done[i].record(self.main)
-            with torch.cuda.stream(self.side):
-                hs = self.ctx.bind_stream()
+            with self.ctx.on(self.side) as hs:
                 self.side.wait_event(self.zslab_done[i])
                 chk(L.afm_factor_masks_f64(hs, T, A_r, lda_r, t0, t1, P(g.vbits), P(part),
                                            P(self.nanfree), P(self.finite)), "factor masks")
-                for src, dst in ((self.nanfree, self.alldf), (self.finite, self.frows)):
-                    chk(L.afm_drop_last_obs_bits_range(hs, T, lda_r, P(g.vbits), P(src), P(dst),
-                                                       t0, t1), "last-obs rows")
+                self._last_obs_rows(hs, t0, t1)
                 if t0 < tr1:
                     if i == 0:
                         self.side.wait_event(self.labels_done)
@@ -565,71 +640,47 @@ class Pipeline:
                                                       P(self.zs), P(self.asset_ok)),
                             "zstats finalize")
                         mark("zstats", 1)
-            h = self.ctx.bind_stream()
         mark("factors", 1)
         self.zstats_done.record(self.side)        # every slab's masks, rows and statistics
         self.main.wait_event(self.zstats_done)
-        chk(L.afm_row_bits(h, self.nch, lda_r, P(self.frows), None, P(self.asset_ok), 0, T,
-                           P(self.zrows)), "z rows")
+        self._zrows(h, 0, self.nch, T)
 
     def _factors_early(self, h, lab_side, mark):
         """The factor panel in two slabs [0, ta) and [ta, T) on the main stream; the train
         window's z statistics (and the z-score row bits of the first slab) on the side stream
         beside the second slab.  Bitwise the same panel, statistics and row sets as one call."""
-        import torch
-        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
-        g, sp, T, lda_r, p, ta = self.g, self.sp, self.T, self.lda_r, self.p, self.ta
-        A_r, wa = self.A_r, self.ta // 64
+        L, P, g, T, ta, wa = _lib.lib(), _lib.ptr, self.g, self.T, self.ta, self.ta // 64
         lab = (None, None) if lab_side else (P(g.ret1d), P(g.excess))
-        chk(L.afm_factors_range_f64(h, T, A_r, lda_r, 0, ta, P(g.close), P(g.volume), *lab,
-                                    P(g.vbits), P(self.out), P(self.nanfree), P(self.finite),
-                                    P(self.fstate)), "factors slab 1")
+
+        def slab(t0, t1):
+            _lib.check(L.afm_factors_range_f64(h, T, self.A_r, self.lda_r, t0, t1, P(g.close),
+                                               P(g.volume), *lab, P(g.vbits), P(self.out),
+                                               P(self.nanfree), P(self.finite), P(self.fstate)),
+                       "factors slab")
+        slab(0, ta)
         if lab_side:
-            with torch.cuda.stream(self.side2):
-                h2 = self.ctx.bind_stream()
-                chk(L.afm_labels_f64(h2, T, lda_r, 0, T, P(g.excess), P(g.ret1d), P(g.vbits),
-                                     P(self.out[TARGET]), P(self.out[TMR])), "labels")
-                self.labels_done.record(self.side2)
-            h = self.ctx.bind_stream()
-        for src, dst in ((self.nanfree, self.alldf), (self.finite, self.frows)):
-            chk(L.afm_drop_last_obs_bits_range(h, T, lda_r, P(g.vbits), P(src), P(dst), 0, ta),
-                "last-obs rows 1")
+            self._labels(self.side2)
+        self._last_obs_rows(h, 0, ta)
         self.slab1_done.record(self.main)
-        with torch.cuda.stream(self.side):
-            hs = self.ctx.bind_stream()
+        with self.ctx.on(self.side) as hs:
             self.side.wait_event(self.slab1_done)
             if lab_side:
                 self.side.wait_event(self.labels_done)          # tmr_ret1d is a feature
             mark("zstats", 0)
-            chk(L.afm_zscore_stats_f64(hs, P(self.out), T * lda_r, T, lda_r, P(self.feat), p,
-                                       P(self.alldf), 0, sp.tr1, P(self.mu), P(self.sd)),
-                "zscore stats")
-            chk(L.afm_zstats_finalize_f64(hs, P(self.mu), P(self.sd), p, lda_r, P(self.zs),
-                                          P(self.asset_ok)), "zstats finalize")
-            chk(L.afm_row_bits(hs, wa, lda_r, P(self.frows), None, P(self.asset_ok), 0, ta,
-                               P(self.zrows)), "z rows 1")
+            self._zstats(hs, wa, ta)
             mark("zstats", 1)
             self.zstats_done.record(self.side)
-        h = self.ctx.bind_stream()
-        chk(L.afm_factors_range_f64(h, T, A_r, lda_r, ta, T, P(g.close), P(g.volume), *lab,
-                                    P(g.vbits), P(self.out), P(self.nanfree), P(self.finite),
-                                    P(self.fstate)), "factors slab 2")
-        for src, dst in ((self.nanfree, self.alldf), (self.finite, self.frows)):
-            chk(L.afm_drop_last_obs_bits_range(h, T, lda_r, P(g.vbits), P(src), P(dst), ta, T),
-                "last-obs rows 2")
+        slab(ta, T)
+        self._last_obs_rows(h, ta, T)
         mark("factors", 1)
         self.main.wait_event(self.zstats_done)
-        chk(L.afm_row_bits(h, self.nch - wa, lda_r, P(self.frows[wa:]), None, P(self.asset_ok),
-                           0, T - ta, P(self.zrows[wa:])), "z rows 2")
+        self._zrows(h, wa, self.nch - wa, T - ta)
 
+    # ---- the step ------------------------------------------------------------------------------
     def step(self, events: dict | None = None):
         """One pass of the chain.  ``events``: optional {stage: (start, end)} CUDA events."""
         import torch
-        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
-        g, c, sp, cm = self.g, self.cfg, self.sp, self.comm
-        T, lda_r, p, W, nch = self.T, self.lda_r, self.p, self.W, self.nch
-        full = self.full
-        caller = torch.cuda.current_stream(full.device)
+        caller = torch.cuda.current_stream(self.full.device)
         for s in self.streams:
             s.wait_stream(caller)
 
@@ -637,190 +688,162 @@ class Pipeline:
             if events is not None and stage in events:
                 events[stage][which].record()
 
-        with torch.cuda.stream(self.main):
-            h = self.ctx.bind_stream()
-            mark("factors", 0)
-            # one GPU: the two label planes on the side stream, enqueued after the factor kernel
-            # (it runs on the CUs the factor workgroups leave free); zstats waits for them
-            lab_side = W == 1 and c.labels_side
-            if self.stream_z:
-                self._factors_streamed(h, lab_side, mark)
-                h = self.ctx.bind_stream()
-            elif self.early:
-                self._factors_early(h, lab_side, mark)
-                h = self.ctx.bind_stream()
-            elif self.A_r > 0:
-                mark("k_factor", 0)
-                chk(L.afm_factors_f64(h, T, self.A_r, lda_r, P(g.close), P(g.volume),
-                                      None if lab_side else P(g.ret1d),
-                                      None if lab_side else P(g.excess), P(g.vbits), P(self.out),
-                                      P(self.nanfree), P(self.finite)), "factors")
-                mark("k_factor", 1)
-                if lab_side:
-                    with torch.cuda.stream(self.side2):
-                        h2 = self.ctx.bind_stream()
-                        chk(L.afm_labels_f64(h2, T, lda_r, 0, T, P(g.excess), P(g.ret1d),
-                                             P(g.vbits), P(self.out[TARGET]), P(self.out[TMR])),
-                            "labels")
-                        self.labels_done.record(self.side2)
-                    h = self.ctx.bind_stream()
-                chk(L.afm_drop_last_obs_bits(h, T, lda_r, P(g.vbits), P(self.nanfree),
-                                             P(self.alldf)), "all_df rows")
-                chk(L.afm_drop_last_obs_bits(h, T, lda_r, P(g.vbits), P(self.finite),
-                                             P(self.frows)), "finite rows")
-            one_pass = not (self.early or self.stream_z)
-            if one_pass:
-                mark("factors", 1)
-            self.fwd_early = c.analyzer and c.early_fwd
-            if self.fwd_early and W == 1:
-                self.side2.wait_stream(self.main)                # the all_df rows
-                with torch.cuda.stream(self.side2):
-                    self._analyzer_fwd()
-                h = self.ctx.bind_stream()
-            if one_pass:
-                mark("zstats", 0)
-            if self.A_r > 0 and one_pass:
-                if lab_side:
-                    self.main.wait_event(self.labels_done)          # tmr_ret1d is a feature
-                chk(L.afm_zscore_stats_f64(h, P(self.out), T * lda_r, T, lda_r, P(self.feat), p,
-                                           P(self.alldf), 0, sp.tr1, P(self.mu), P(self.sd)),
-                    "zscore stats")
-                chk(L.afm_zstats_finalize_f64(h, P(self.mu), P(self.sd), p, lda_r, P(self.zs),
-                                              P(self.asset_ok)), "zstats finalize")
-                chk(L.afm_row_bits(h, nch, lda_r, P(self.frows), None, P(self.asset_ok), 0, T,
-                                   P(self.zrows)), "z rows")
-            if one_pass:
-                mark("zstats", 1)
-            if W > 1:           # full-width label planes for the rebalance, during the Grams
-                with torch.cuda.stream(self.side2):
-                    h2 = self.ctx.bind_stream()
-                    chk(L.afm_labels_f64(h2, T, full.lda, self.lab0, T, P(full.excess),
-                                         P(full.ret1d), P(full.vbits), P(self.target),
-                                         P(self.tmr)), "labels")
-                    self.labels_done.record(self.side2)
-                if self.fwd_early:
-                    # the analyzer's price rows and forward returns need the whole cross-section's
-                    # all_df rows only (not the predictions): gathered now, beside the Grams, so
-                    # the analyzer's prediction-dependent chain starts right at the predict
-                    self.side2.wait_stream(self.main)            # the all_df rows (after zstats)
-                    with torch.cuda.stream(self.side2):
-                        self._gather_alldf()
-                        self._analyzer_fwd()
-                h = self.ctx.bind_stream()
-            mark("xs_gram", 0)
-            self._pooled_blocks(h, 0, sp.v1, mark)                  # train + valid rows
-            if sp.dup:                                              # train_end counted twice
-                self._te_subtree(h, sp.tr1 - 1)
-            if W > 1:
-                mark("exchange", 0)
-                gb = cm.all_gather(self.pool_blk)                   # [W][nblk_r + 1][part]
-                self.pool_all.copy_(gb[:, :self.nblk_r].reshape(N_BLOCKS, self.pe))
-                self.te_all.copy_(gb[:, self.nblk_r])
-                mark("exchange", 1)
-                h = self.ctx.bind_stream()
-                blocks, te_leaves, nte = self.pool_all, self.te_all, W
-            else:
-                blocks, te_leaves, nte = self.pool_blk, self.pool_blk[self.nblk_r:], 1
-            chk(L.afm_gram_tree_f64(h, p, P(blocks), N_BLOCKS, N_BLOCKS, 1, P(self.pool_g)),
-                "tree blocks")
-            if sp.dup:
-                chk(L.afm_gram_tree_f64(h, p, P(te_leaves), nte, nte, 1, P(self.te_gram)),
-                    "tree train_end")
-                chk(L.afm_vec_add_f64(h, self.p2 * self.p2, P(self.te_gram), P(self.pool_g)),
-                    "dup")
-            mark("xs_gram", 1)
-            # side stream: this shard's per-date FM30 partials (nothing downstream reads them),
-            # forked after the pooled Gram -- run beside it, both MFMA kernels slow down (A/B on
-            # MI355X: pooled Gram 12.7 ms alone, 23 ms beside the FM Grams).  One GPU: forked
-            # after the predict, ahead of the analyzer (A/B over 5 runs: 35.29 vs 35.40 ms/step
-            # forked after the Gram; 36.4-37.0 after the analyzer, 36.5-36.7 after the
-            # rebalance).  AFM_FM_FORK=gram|predict|analyzer|rebalance: A/B.
-            def fork_fm():
-                self.side.wait_stream(self.main)
-                with torch.cuda.stream(self.side):
-                    hs = self.ctx.bind_stream()
-                    mark("fm", 0)
-                    self._fm_local(hs)
-                    if W == 1:
-                        self._fm_solve(hs, self.fm_sub)
-                        self._fm_stats(hs)
-                    mark("fm", 1)
-                return self.ctx.bind_stream()
-
-            fm_at = c.fm_fork if W == 1 else "gram"
-            if fm_at == "gram":
-                h = fork_fm()
-            mark("lasso", 0)
-            chk(L.afm_lasso_fit_f64(h, P(self.pool_g), P(self.pool_s), p, c.alpha, c.max_iter,
-                                    c.lasso_tol, 0, P(self.lasso_beta), P(self.lasso_info)),
-                "lasso")
-            mark("lasso", 1)
-            mark("predict", 0)
-            if self.A_r > 0:
-                chk(L.afm_zpredict_f64(h, P(self.out), T * lda_r, lda_r, sp.s0, T - sp.s0,
-                                       P(self.feat), p, P(self.zs), P(self.lasso_beta),
-                                       P(self.zrows), P(self.pred_r)), "predict")
-            if W > 1:                          # the whole cross-section of the test dates
-                self._gather_test_planes()
-                h = self.ctx.bind_stream()
-            mark("predict", 1)
-            if fm_at == "predict":
-                h = fork_fm()
-            if c.analyzer:
-                self.side2.wait_stream(self.main)
-                with torch.cuda.stream(self.side2):
-                    self._analyzer(mark)
-                h = self.ctx.bind_stream()
-            if fm_at == "analyzer":
-                h = fork_fm()
-            mark("rebalance", 0)
-            if W > 1:
-                self.main.wait_event(self.labels_done)     # the label planes
-            x = self.reb_ext
-            ne = self.e1 - self.e0
-            if ne > 0:
-                chk(L.afm_rebalance_f64(h, T, full.A, full.lda, P(self.rd_ext), ne, P(self.pred),
-                                        P(full.tbits), P(self.target), P(self.zrows_full), 0,
-                                        sp.tr1, -1 if c.window is None else int(c.window),
-                                        P(full.close), P(self.tmr), c.top_n, c.lo, c.hi,
-                                        P(x["k"]), P(x["books"]), P(x["weights"]), P(x["sums"]),
-                                        P(x["upos"]), P(x["usize"]), P(x["status"])), "rebalance")
-            if self.reb_split:
-                self._gather_rebalance()
-                h = self.ctx.bind_stream()
-            mark("rebalance", 1)
-            if fm_at == "rebalance":
-                h = fork_fm()
-            r, q = self.reb, self.pnl
-
-            def pnl_scan(hh):
-                mark("pnl", 0)
-                chk(L.afm_pnl_scan_f64(hh, self.nd, P(r["k"]), P(r["books"]), P(r["sums"]),
-                                       P(r["upos"]), P(r["usize"]), c.v0, c.rate, P(q["value"]),
-                                       P(q["turnover"]), P(q["long_ret"]), P(q["short_ret"])),
-                    "pnl")
-                mark("pnl", 1)
-            if W == 1:
-                pnl_scan(h)
-            else:
-                # the scan on its own stream; the FM exchange (per-date subtrees -> date owners,
-                # solves, betas) and the analyzer's gather + series run beside it on the main and
-                # second side streams, issued in this order on every rank (RCCL runs a group's
-                # collectives in issue order)
-                self.side3.wait_stream(self.main)
-                with torch.cuda.stream(self.side3):
-                    pnl_scan(self.ctx.bind_stream())
-                h = self.ctx.bind_stream()
-                self.main.wait_stream(self.side)
-                self._fm_exchange()
-                if c.analyzer:
-                    with torch.cuda.stream(self.side2):
-                        self._analyzer_series(mark)
+        with self.ctx.on(self.main) as h:
+            self._stage_factors(h, mark)
+            self._stage_gram(h, mark)
+            self._stage_fit_predict(h, mark)
+            self._stage_tail(h, mark)
         for s in self.streams:
             caller.wait_stream(s)
-        self.ctx.bind_stream()
 
-    # ---- exchanges (N > 1) -------------------------------------------------------------------
+    def _stage_factors(self, h, mark):
+        """factors + zstats: the panel, the row sets and the train window's z statistics; the
+        prediction-independent side work (label planes, the analyzer's forward returns) forked."""
+        W, one_pass = self.W, not (self.early or self.stream_z)
+        lab_side = W == 1 and self.cfg.labels_side
+        mark("factors", 0)
+        if self.stream_z:
+            self._factors_streamed(h, lab_side, mark)
+        elif self.early:
+            self._factors_early(h, lab_side, mark)
+        else:
+            self._factors_one_pass(h, lab_side, mark)
+        if self.fwd_early and W == 1:
+            self.side2.wait_stream(self.main)                # the all_df rows
+            with self.ctx.on(self.side2) as h2:
+                self._analyzer_fwd(h2)
+        if one_pass:
+            mark("zstats", 0)
+            if self.A_r > 0:
+                if lab_side:
+                    self.main.wait_event(self.labels_done)          # tmr_ret1d is a feature
+                self._zstats(h, self.nch, self.T)
+            mark("zstats", 1)
+        if W > 1:           # full-width label planes for the rebalance, during the Grams
+            self._labels(self.side2, full=True)
+            if self.fwd_early:
+                # the analyzer's price rows and forward returns need the whole cross-section's
+                # all_df rows only (not the predictions): gathered now, beside the Grams, so
+                # the analyzer's prediction-dependent chain starts right at the predict
+                self.side2.wait_stream(self.main)            # the all_df rows (after zstats)
+                with self.ctx.on(self.side2) as h2:
+                    self._gather_alldf()
+                    self._analyzer_fwd(h2)
+
+    def _stage_gram(self, h, mark):
+        """xs_gram: the pooled Gram of the train + valid rows (block results, N > 1: exchanged,
+        then the block level of the tree), train_end's Gram added once more."""
+        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
+        sp, p, W = self.sp, self.p, self.W
+        mark("xs_gram", 0)
+        self._pooled_blocks(h, 0, sp.v1, mark=mark)             # train + valid rows
+        if sp.dup:                                              # train_end counted twice
+            self._te_subtree(h, sp.tr1 - 1)
+        if W > 1:
+            mark("exchange", 0)
+            gb = self.comm.all_gather(self.pool_blk)            # [W][nblk_r + 1][part]
+            self.pool_all.copy_(gb[:, :self.nblk_r].reshape(N_BLOCKS, self.pe))
+            self.te_all.copy_(gb[:, self.nblk_r])
+            mark("exchange", 1)
+            blocks, te_leaves, nte = self.pool_all, self.te_all, W
+        else:
+            blocks, te_leaves, nte = self.pool_blk, self.pool_blk[self.nblk_r:], 1
+        chk(L.afm_gram_tree_f64(h, p, P(blocks), N_BLOCKS, N_BLOCKS, 1, P(self.pool_g)),
+            "tree blocks")
+        if sp.dup:
+            chk(L.afm_gram_tree_f64(h, p, P(te_leaves), nte, nte, 1, P(self.te_gram)),
+                "tree train_end")
+            chk(L.afm_vec_add_f64(h, self.p2 * self.p2, P(self.te_gram), P(self.pool_g)), "dup")
+        mark("xs_gram", 1)
+
+    def _fork_fm(self, at, mark):
+        """Side stream, if the FM fork point is ``at``: this shard's per-date FM30 partials
+        (nothing downstream reads them), forked after the pooled Gram -- run beside it, both MFMA
+        kernels slow down (A/B on MI355X: pooled Gram 12.7 ms alone, 23 ms beside the FM Grams).
+        One GPU: forked after the predict, ahead of the analyzer (A/B over 5 runs: 35.29 vs
+        35.40 ms/step forked after the Gram; 36.4-37.0 after the analyzer, 36.5-36.7 after the
+        rebalance); ``PipelineConfig.fm_fork`` moves it."""
+        if at != self.fm_at:
+            return
+        self.side.wait_stream(self.main)
+        with self.ctx.on(self.side) as hs:
+            mark("fm", 0)
+            self._fm_local(hs)
+            if self.W == 1:
+                self._fm_solve(hs, self.fm_sub)
+                self._fm_stats(hs)
+            mark("fm", 1)
+
+    def _stage_fit_predict(self, h, mark):
+        """lasso + predict (N > 1: the test dates' whole cross-section gathered)."""
+        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
+        c, sp, T, lda_r, p = self.cfg, self.sp, self.T, self.lda_r, self.p
+        self._fork_fm("gram", mark)
+        mark("lasso", 0)
+        chk(L.afm_lasso_fit_f64(h, P(self.pool_g), P(self.pool_s), p, c.alpha, c.max_iter,
+                                c.lasso_tol, 0, P(self.lasso_beta), P(self.lasso_info)), "lasso")
+        mark("lasso", 1)
+        mark("predict", 0)
+        if self.A_r > 0:
+            chk(L.afm_zpredict_f64(h, P(self.out), T * lda_r, lda_r, sp.s0, T - sp.s0,
+                                   P(self.feat), p, P(self.zs), P(self.lasso_beta),
+                                   P(self.zrows), P(self.pred_r)), "predict")
+        if self.W > 1:                          # the whole cross-section of the test dates
+            self._gather_test_planes()
+        mark("predict", 1)
+        self._fork_fm("predict", mark)
+
+    def _stage_tail(self, h, mark):
+        """The analyzer forked onto the second side stream; rebalance and pnl on the main stream;
+        N > 1: the scan on its own stream beside the FM exchange and the analyzer's series."""
+        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
+        c, sp, full, W = self.cfg, self.sp, self.full, self.W
+        if c.analyzer:
+            self.side2.wait_stream(self.main)
+            with self.ctx.on(self.side2) as h2:
+                self._analyzer(h2, mark)
+        self._fork_fm("analyzer", mark)
+        mark("rebalance", 0)
+        if W > 1:
+            self.main.wait_event(self.labels_done)     # the label planes
+        x, ne = self.reb_ext, self.e1 - self.e0
+        if ne > 0:
+            chk(L.afm_rebalance_f64(h, self.T, full.A, full.lda, P(self.rd_ext), ne, P(self.pred),
+                                    P(full.tbits), P(self.target), P(self.zrows_full), 0,
+                                    sp.tr1, -1 if c.window is None else int(c.window),
+                                    P(full.close), P(self.tmr), c.top_n, c.lo, c.hi,
+                                    P(x["k"]), P(x["books"]), P(x["weights"]), P(x["sums"]),
+                                    P(x["upos"]), P(x["usize"]), P(x["status"])), "rebalance")
+        if self.reb_split:
+            self._gather_rebalance()
+        mark("rebalance", 1)
+        self._fork_fm("rebalance", mark)
+        if W == 1:
+            self._pnl_scan(h, mark)
+            return
+        # the scan on its own stream; the FM exchange (per-date subtrees -> date owners, solves,
+        # betas) and the analyzer's gather + series run beside it on the main and second side
+        # streams, issued in this order on every rank (RCCL runs a group's collectives in issue
+        # order)
+        self.side3.wait_stream(self.main)
+        with self.ctx.on(self.side3) as h3:
+            self._pnl_scan(h3, mark)
+        self.main.wait_stream(self.side)
+        self._fm_exchange(h)
+        if c.analyzer:
+            with self.ctx.on(self.side2) as h2:
+                self._analyzer_series(h2, mark)
+
+    def _pnl_scan(self, h, mark):
+        L, P, c, r, q = _lib.lib(), _lib.ptr, self.cfg, self.reb, self.pnl
+        mark("pnl", 0)
+        _lib.check(L.afm_pnl_scan_f64(h, self.nd, P(r["k"]), P(r["books"]), P(r["sums"]),
+                                      P(r["upos"]), P(r["usize"]), c.v0, c.rate, P(q["value"]),
+                                      P(q["turnover"]), P(q["long_ret"]), P(q["short_ret"])),
+                   "pnl")
+        mark("pnl", 1)
+
+    # ---- exchanges (N > 1; a collective runs on the current stream and leaves the binding) ----
     def _send_buffer(self, key, specs, device):
         """The persistent packed send buffer of one exchange (made on its first step)."""
         from .packing import SendBuffer
@@ -829,23 +852,40 @@ class Pipeline:
             sb = self._send[key] = SendBuffer(specs, device)
         return sb
 
-    def _gather_analyzer(self):
-        """The per-date analyzer results of every rank's date share -> the full arrays (one
-        packed all-gather, shares padded to the largest)."""
+    def _place_shares(self, key, ranges, gathered, dsts):
+        """All-gathered date shares ``gathered[i]`` [W][largest share][...] -> ``dsts[i]`` in
+        global order: ONE index_select per array (the row index cached under ``key``), not one
+        copy per rank."""
         import torch
-        an, (j0, j1), n = self.an, self.an_rng, self.an_nmax
-        keys = ("ic", "layer_mean", "layer_cnt", "port")
-        sb = self._send_buffer("an", [((n,) + tuple(an[k].shape[1:]), an[k].dtype, 0)
-                                      for k in keys], an["ic"].device)
-        for k, part in zip(keys, sb.parts):          # rows past the share stay zero
-            part[:j1 - j0].copy_(an[k][j0:j1])
-        got = self.comm.all_gather_buffer(sb)
-        if self._an_rows is None:           # gathered row (rank q, j) of every analyzer date
-            self._an_rows = _share_rows([_even(self.an_nd, self.W, q) for q in range(self.W)], n,
-                                        an["ic"].device)
-        for k, g in zip(keys, got):         # one gather per key, not one copy per rank
-            torch.index_select(g.reshape((-1,) + tuple(g.shape[2:])), 0, self._an_rows,
-                               out=an[k][:self.an_nd])
+        rows = self._rows.get(key)
+        if rows is None:                    # gathered row (rank q, i) of every date
+            rows = self._rows[key] = _share_rows(ranges, gathered[0].shape[1],
+                                                 gathered[0].device)
+        if rows.numel():
+            for g, dst in zip(gathered, dsts):
+                torch.index_select(g.reshape((-1,) + tuple(g.shape[2:])), 0, rows, out=dst)
+
+    def _gather_shares(self, key, srcs, own, ranges, dsts):
+        """This rank's share (rows ``own[0]:own[1]``) of every array of ``srcs``, padded to the
+        largest share, in one packed all-gather -> every rank's share placed in ``dsts``."""
+        n = max(b - a for a, b in ranges)
+        sb = self._send_buffer(key, [((n,) + tuple(v.shape[1:]), v.dtype, 0) for v in srcs],
+                               srcs[0].device)
+        for v, part in zip(srcs, sb.parts):          # rows past the share stay zero
+            part[:own[1] - own[0]].copy_(v[own[0]:own[1]])
+        self._place_shares(key, ranges, self.comm.all_gather_buffer(sb), dsts)
+
+    def _gather_analyzer(self):
+        """The per-date analyzer results of every rank's date share -> the full arrays."""
+        srcs = [self.an[k] for k in ("ic", "layer_mean", "layer_cnt", "port")]
+        self._gather_shares("an", srcs, self.an_rng, self.an_ranges,
+                            [v[:self.an_nd] for v in srcs])
+
+    def _gather_rebalance(self):
+        """The books of every rank's share of the rebalance dates -> ``reb``."""
+        lo = self.i0 - self.e0
+        self._gather_shares("reb", list(self.reb_ext.values()), (lo, lo + self.i1 - self.i0),
+                            self.rrange, [v[:self.nd] for v in self.reb.values()])
 
     def _place(self, dst, gathered, rows=None):
         """Scatter per-rank shard columns ([W][rows][wide]) into a full-width plane.  Rank q's
@@ -900,53 +940,28 @@ class Pipeline:
             sb.parts[0][:, :self.A_r].copy_(self.alldf[:, :self.A_r])
         self._place(self.alldf_full, self.comm.all_gather_buffer(sb)[0])
 
-    def _gather_rebalance(self):
-        import torch
-        x = self.reb_ext
-        lo = self.i0 - self.e0
-        n_own = self.i1 - self.i0
-        sb = self._send_buffer("reb", [((self.nr_max,) + tuple(v.shape[1:]), v.dtype, 0)
-                                       for v in x.values()], x["k"].device)
-        for v, part in zip(x.values(), sb.parts):    # rows past the share stay zero
-            part[:n_own].copy_(v[lo:lo + n_own])
-        if self._reb_rows is None:          # gathered row (rank q, i) of every rebalance date
-            self._reb_rows = _share_rows(self.rrange, self.nr_max, x["k"].device)
-        for k, gath in zip(x.keys(), self.comm.all_gather_buffer(sb)):
-            if self.nd > 0:                 # one gather per key, not one copy per rank
-                torch.index_select(gath.reshape((-1,) + tuple(gath.shape[2:])), 0,
-                                   self._reb_rows, out=self.reb[k][:self.nd])
-
-    def _fm_exchange(self):
-        import torch
-        W, pef = self.W, self.pef
-        splits = [b - a for a, b in self.fdr]
-        recv = self.comm.all_to_all(self.fm_sub, splits, [self.fnd] * W)   # [W * fnd][part]
-        sub = recv.view(W, self.fnd, pef).transpose(0, 1).contiguous()     # [fnd][W][part]
-        h = self.ctx.bind_stream()
+    def _fm_exchange(self, h):
+        """The per-date subtrees to the date owners (one all_to_all), their solves, then every
+        rank gets every date's betas (one packed all-gather) and the FM statistics."""
+        W = self.W
+        recv = self.comm.all_to_all(self.fm_sub, [b - a for a, b in self.fdr],
+                                    [self.fnd] * W)                          # [W * fnd][part]
+        sub = recv.view(W, self.fnd, self.pef).transpose(0, 1).contiguous()   # [fnd][W][part]
         self._fm_solve(h, sub)
         got = self.comm.all_gather_packed([self.fm_beta_own, self.fm_nobs_own, self.fm_rank_own])
-        if self._fm_rows is None:           # gathered row (rank q, i) of every FM date
-            self._fm_rows = _share_rows(self.fdr, self.fnd_max, self.fm_beta.device)
-        for g, dst in zip(got, (self.fm_beta, self.fm_nobs, self.fm_rank)):
-            torch.index_select(g.reshape((-1,) + tuple(g.shape[2:])), 0, self._fm_rows, out=dst)
-        self._fm_stats(self.ctx.bind_stream())
+        self._place_shares("fm", self.fdr, got, (self.fm_beta, self.fm_nobs, self.fm_rank))
+        self._fm_stats(h)
 
-    def _fm_stats(self, h):
-        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
-        chk(L.afm_fama_macbeth_f64(h, P(self.fm_beta), P(self.fm_rank), self.T, self.pf + 1,
-                                   P(self.fm_mean), P(self.fm_t)), "fama_macbeth")
-
-    # ------------------------------------------------------------------------------------------
-    def _analyzer(self, mark):
+    # ---- the analyzer (second side stream) ------------------------------------------------------
+    def _analyzer(self, h, mark):
         """AlphaSignalAnalyzer(lasso_predict, price_data=df_test[['close_price']]).run()
         (KKT:630-631) on the test sub-grid, no host synchronisation."""
         L, P, chk = _lib.lib(), _lib.ptr, _lib.check
         full, sp, an = self.full, self.sp, self.an
         lda, a0, Ta = full.lda, self.an_a0, self.Ta
-        h = self.ctx.bind_stream()
         mark("analyzer", 0)
         if not self.fwd_early:
-            self._analyzer_fwd()
+            self._analyzer_fwd(h)
         j0, j1 = self.an_rng
         d0 = sp.s0 - a0 + j0                        # sub-grid dates [d0, d1) of this rank
         d1 = d0 + (j1 - j0)
@@ -963,50 +978,35 @@ class Pipeline:
                                    P(an["port"][j0:])), "xs_stats")
         if self.W > 1:
             return          # the all-gather and the series follow the main chain's exchanges
-        self._analyzer_series(mark)
+        self._analyzer_series(h, mark)
 
-    def _analyzer_fwd(self):
+    def _analyzer_fwd(self, h):
         """The analyzer's df_test price rows and forward returns (KKT:294-296): they read the close
         plane and the all_df rows only, not the predictions."""
         L, P, chk = _lib.lib(), _lib.ptr, _lib.check
         full, sp, an, a0 = self.full, self.sp, self.an, self.an_a0
-        h = self.ctx.bind_stream()
         chk(L.afm_row_bits(h, self.nch, full.lda, P(self.alldf_full), None, None, sp.s0, self.T,
                            P(self.price_bits)), "price rows")
-        cb = a0 // 64
         chk(L.afm_fwd_returns_f64(h, self.Ta, full.lda, P(full.close[a0:]),
-                                  P(self.price_bits[cb:]), P(an["fr"])), "fwd_returns")
+                                  P(self.price_bits[a0 // 64:]), P(an["fr"])), "fwd_returns")
 
-    def _analyzer_series(self, mark):
+    def _analyzer_series(self, h, mark):
         L, P, chk = _lib.lib(), _lib.ptr, _lib.check
         an = self.an
         if self.W > 1:
             self._gather_analyzer()
-        h = self.ctx.bind_stream()
         chk(L.afm_xs_series_f64(h, self.an_nd, P(an["layer_mean"]), P(an["port"]), P(an["ic"]),
                                 P(self.an_year), self.an_nyears, self.an_year0,
                                 P(an["cum_layer"]), P(an["ls"]), P(an["cum_port"]), P(an["ir"]),
                                 P(an["ir_scratch"])), "xs_series")
         mark("analyzer", 1)
 
-    # ------------------------------------------------------------------------------------------
     def _range_gram(self, h, t0, nt, bufs, gram):
         """The pooled Gram of the z-score rows of the dates [t0, t0 + nt) -> gram [1][p+2][p+2]:
-        the partials and tree of ``_pooled_blocks`` + the block level, in the buffers ``bufs`` (not
-        the step's)."""
-        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
-        T, lda, p = self.T, self.lda_r, self.p
-        part, c1b, rb, blk = bufs
-        blk.zero_()
-        chk(L.afm_zpool_f64(h, P(self.out), T * lda, lda, P(self.feat), None, p, TARGET,
-                            P(self.zs), p, P(self.zrows), t0, nt, 0, self.nrb, self.A_r,
-                            N_CHUNKS, P(part), 0), "zpool")
-        c1, c2 = CHUNK_TREE
-        chk(L.afm_gram_tree_f64(h, p, P(part), self.nrb * N_CHUNKS, c1, 0, P(c1b)), "tree chunks")
-        chk(L.afm_gram_tree_f64(h, p, P(c1b), self.nrb * c2, c2, 0, P(rb)), "tree chunks 2")
-        chk(L.afm_gram_tree_f64(h, p, P(rb), self.nrb, self.rb_per_blk, 0, P(blk)),
-            "tree row-blocks")
-        chk(L.afm_gram_tree_f64(h, p, P(blk), N_BLOCKS, N_BLOCKS, 1, P(gram)), "tree blocks")
+        ``_pooled_blocks`` in the buffers ``bufs`` (not the step's) + the block level."""
+        self._pooled_blocks(h, t0, nt, bufs)
+        _lib.check(_lib.lib().afm_gram_tree_f64(h, self.p, _lib.ptr(bufs[3]), N_BLOCKS, N_BLOCKS,
+                                                1, _lib.ptr(gram)), "tree blocks")
 
     def lasso_cv(self, alphas=None, *, n_alphas: int = 100, eps: float = 1e-3) -> dict:
         """Validation-scored alpha selection on the last ``step()``'s panel (one GPU): the
@@ -1036,21 +1036,21 @@ class Pipeline:
             self._cv_gram = torch.empty((2, self.p2, self.p2), dtype=torch.float64,
                                         device=self.out.device)
         gram, shift = self._cv_gram, self.pool_s.expand(2, self.p2).contiguous()
-        h = self.ctx.bind_stream()
-        self._range_gram(h, 0, sp.tr1, self._cv_bufs, gram[0:1])
-        self._range_gram(h, sp.v0, sp.v1 - sp.v0, self._cv_bufs, gram[1:2])
-        a = _given_alphas(alphas) if alphas is not None else \
-            alpha_grid(gram[0].cpu().numpy(), p, eps, n_alphas)
-        beta, info = lasso_batch(gram[0:1], shift[0:1], p, torch.from_numpy(a).to(gram.device),
-                                 nprob=1, warm=True, max_iter=c.max_iter, tol=c.lasso_tol)
-        score = gram_score(gram[1:2], shift[1:2], p, beta).cpu().numpy()[0]
-        n_train = float(gram[0, 0, 0].item())
-        best = int(np.argmin(score[:, 1]))
-        refit = torch.empty(p + 1, dtype=torch.float64, device=gram.device)
-        rinfo = torch.empty(3, dtype=torch.float64, device=gram.device)
-        chk(L.afm_lasso_fit_f64(self.ctx.bind_stream(), P(self.pool_g), P(self.pool_s), p,
-                                float(a[best]), c.max_iter, c.lasso_tol, 0, P(refit), P(rinfo)),
-            "lasso refit")
+        with self.ctx.on(torch.cuda.current_stream(self.out.device)) as h:   # the caller's stream
+            self._range_gram(h, 0, sp.tr1, self._cv_bufs, gram[0:1])
+            self._range_gram(h, sp.v0, sp.v1 - sp.v0, self._cv_bufs, gram[1:2])
+            a = _given_alphas(alphas) if alphas is not None else \
+                alpha_grid(gram[0].cpu().numpy(), p, eps, n_alphas)
+            beta, info = lasso_batch(gram[0:1], shift[0:1], p, torch.from_numpy(a).to(gram.device),
+                                     nprob=1, warm=True, max_iter=c.max_iter, tol=c.lasso_tol)
+            score = gram_score(gram[1:2], shift[1:2], p, beta).cpu().numpy()[0]
+            n_train = float(gram[0, 0, 0].item())
+            best = int(np.argmin(score[:, 1]))
+            refit = torch.empty(p + 1, dtype=torch.float64, device=gram.device)
+            rinfo = torch.empty(3, dtype=torch.float64, device=gram.device)
+            chk(L.afm_lasso_fit_f64(h, P(self.pool_g), P(self.pool_s), p, float(a[best]),
+                                    c.max_iter, c.lasso_tol, 0, P(refit), P(rinfo)),
+                "lasso refit")
         info_h = info[0].cpu().numpy()
         return {"alphas": a, "coefs": beta[0].cpu().numpy(),
                 "n_iter": info_h[:, 2].astype(np.int64), "dual_gap": info_h[:, 0] / n_train,

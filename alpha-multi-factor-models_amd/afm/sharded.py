@@ -22,7 +22,7 @@ tensors are staged through host memory (CPU tests, or several ranks sharing one 
 from __future__ import annotations
 
 from .grid import PanelGrid
-from .pipeline import EXCHANGE_STAGES, Pipeline, PipelineConfig  # noqa: F401
+from .pipeline import EXCHANGE_STAGES, Pipeline, PipelineConfig, even_range  # noqa: F401
 
 
 def block_range(n: int, world: int, rank: int, unit: int = 64):
@@ -31,10 +31,6 @@ def block_range(n: int, world: int, rank: int, unit: int = 64):
     nb = (n + unit - 1) // unit
     b0, b1 = nb * rank // world, nb * (rank + 1) // world
     return min(unit * b0, n), min(unit * b1, n)
-
-
-def even_range(n: int, world: int, rank: int):
-    return n * rank // world, n * (rank + 1) // world
 
 
 class Comm:

@@ -134,7 +134,9 @@ def test_fama_macbeth_vs_golden(chain_a):
                                    {"early_zstats": True, "zstats_slabs": 0},
                                    {"early_zstats": True, "labels_side": False, "zstats_slabs": 0},
                                    {"early_fwd": False}, {"zstats_slabs": 0},
-                                   {"zstats_slabs": 3}, {"zstats_slabs": 6, "labels_side": False}])
+                                   {"zstats_slabs": 3}, {"zstats_slabs": 6, "labels_side": False},
+                                   {"fm_fork": "analyzer"}, {"main_priority": False},
+                                   {"fm_grid": 64}])
 def test_stream_placement_bit_identical(chain_a, place):
     """The side-stream placements (label planes beside the factor kernel, the FM fork point) move
     work between streams only: the step's outputs are bitwise those of the default placement.
