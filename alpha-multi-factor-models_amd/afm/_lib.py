@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import operator
 import os
 import threading
 
@@ -20,73 +21,85 @@ I64 = ctypes.c_int64
 I32 = ctypes.c_int
 DBL = ctypes.c_double
 
-# name -> (restype, argtypes); kept in sync with include/afm.h (tests/test_abi.py checks it)
+# name -> (return, parameters) as include/afm.h declares them (tests/test_abi.py compares every
+# prototype with this table).  Return: "status" (int: 0 or an AFM_E* code), "int" / "i64" (a value,
+# negative on failure), "str".  Parameters: ctx (afm_ctx*), int, i64, f64, str (const char*);
+# device buffers by element type -- f64*, i32*, i64* (int64_t / uint64_t: torch.int64 words);
+# ptr: opaque (void*, afm_ctx**, a host array); host:i64*: a host int64_t.
 SIGNATURES = {
-    "afm_ctx_create": (I32, [I32, ctypes.POINTER(P)]),
-    "afm_ctx_set_stream": (I32, [P, P]),
-    "afm_ctx_set_option": (I32, [P, ctypes.c_char_p, I64]),
-    "afm_ctx_get_option": (I32, [P, ctypes.c_char_p, ctypes.POINTER(I64)]),
-    "afm_stream_create_cu_mask": (I32, [I32, P, I32, ctypes.POINTER(P)]),
-    "afm_stream_destroy": (I32, [P]),
-    "afm_ctx_destroy": (I32, [P]),
-    "afm_last_error": (ctypes.c_char_p, []),
-    "afm_version": (I32, []),
-    "afm_factor_name": (ctypes.c_char_p, [I32]),
-    "afm_factors_f64": (I32, [P, I64, I64, I64, P, P, P, P, P, P, P, P]),
-    "afm_factors_state_bytes": (I64, [P, I64]),
-    "afm_factors_slab_f64": (I32, [P, I64, I64, I64, I64, I64, P, P, P, P, P, P, P, P, P]),
-    "afm_factors_range_f64": (I32, [P, I64, I64, I64, I64, I64, P, P, P, P, P, P, P, P, P]),
-    "afm_xs_gram_f64": (I32, [P, P, I64, I64, I64, I64, P, I32, I32, P, I64, I64, P, P]),
-    "afm_ols_solve_f64": (I32, [P, P, P, I32, I64, DBL, P, P, P]),
-    "afm_pool_moments_f64": (I32, [P, P, P, I32, I64, P, P]),
-    "afm_pool_tree_f64": (I32, [P, P, P, I32, I64, I32, P, P]),
-    "afm_pool_segments_f64": (I32, [P, P, P, I32, I64, I64, P, P]),
-    "afm_labels_f64": (I32, [P, I64, I64, I64, I64, P, P, P, P, P]),
-    "afm_drop_last_obs_bits": (I32, [P, I64, I64, P, P, P]),
-    "afm_drop_last_obs_bits_range": (I32, [P, I64, I64, P, P, P, I64, I64]),
-    "afm_factors_part_words": (I64, [P, I64, I64, I64, I64]),
-    "afm_factors_range_part_f64": (I32, [P, I64, I64, I64, I64, I64, P, P, P, P, P, P]),
-    "afm_factor_masks_f64": (I32, [P, I64, I64, I64, I64, I64, P, P, P, P]),
-    "afm_predict_f64": (I32, [P, P, I64, I64, I64, I64, P, I32, P, I64, P, I32, P]),
-    "afm_fama_macbeth_f64": (I32, [P, P, P, I64, I32, P, P]),
-    "afm_ols_residual_f64": (I32, [P, P, I64, I32, I32, P, P, P]),
-    "afm_vec_add_f64": (I32, [P, I64, P, P]),
-    "afm_ols_intercept_f64": (I32, [P, I32, P, P]),
-    "afm_lasso_cd_f64": (I32, [P, P, I32, DBL, DBL, I32, DBL, I32, P, P]),
-    "afm_talib_factors_f64": (I32, [P, I64, I64, I64, P, P, P, P]),
-    "afm_ffill_f64": (I32, [P, I64, I64, I64, P, P]),
-    "afm_date_mean_fill_f64": (I32, [P, I64, I64, I64, I64, P, P, P]),
-    "afm_group_demean_f64": (I32, [P, I64, P, I64, P, P, P]),
-    "afm_rebalance_f64": (I32, [P, I64, I64, I64, P, I64, P, P, P, P, I64, I64, I64, P, P, I32,
-                                DBL, DBL, P, P, P, P, P, P, P]),
-    "afm_pnl_scan_f64": (I32, [P, I64, P, P, P, P, P, DBL, DBL, P, P, P, P]),
-    "afm_bootstrap_pnl_f64": (I32, [P, I64, P, I64, P, P, P, P, I64, I64, P, DBL, DBL, P, P, P,
-                                    P]),
-    "afm_min_variance_weights_f64": (I32, [P, P, I64, I64, I32, DBL, DBL, P, P, P]),
-    "afm_fwd_returns_f64": (I32, [P, I64, I64, P, P, P]),
-    "afm_xs_prepare_f64": (I32, [P, I64, I64, I64, P, P, P, P, P, P]),
-    "afm_xs_prepare_range_f64": (I32, [P, I64, I64, I64, I64, I64, P, P, P, P, P, P]),
-    "afm_xs_rank_f64": (I32, [P, I64, I64, P, P, P, P, P, P]),
-    "afm_xs_layers_f64": (I32, [P, I64, I64, P, P, P, P, P, P]),
-    "afm_xs_stats_f64": (I32, [P, I64, I64, P, I64, P, P, P, P, I32, P, P, P, P]),
-    "afm_xs_series_f64": (I32, [P, I64, P, P, P, P, I32, I32, P, P, P, P, P]),
-    "afm_zscore_stats_f64": (I32, [P, P, I64, I64, I64, P, I32, P, I64, I64, P, P]),
-    "afm_zscore_stats_slab_f64": (I32, [P, P, I64, I64, I64, P, I32, P, I64, I64, P, I32, I32,
-                                        P, P]),
-    "afm_zscore_apply_f64": (I32, [P, P, I64, I64, I64, P, I32, P, I64, I64, P, P, P, I64, P, P]),
-    "afm_zgram_part_bytes": (I32, [I32]),
-    "afm_zstats_finalize_f64": (I32, [P, P, P, I32, I64, P, P]),
-    "afm_row_bits": (I32, [P, I64, I64, P, P, P, I64, I64, P]),
-    "afm_zgram_f64": (I32, [P, P, I64, I64, P, P, I32, I32, P, I32, P, I64, I64, I32, I64, I64,
-                            I64, P, I32]),
-    "afm_zpool_f64": (I32, [P, P, I64, I64, P, P, I32, I32, P, I32, P, I64, I64, I64, I32, I64,
-                            I32, P, I32]),
-    "afm_gram_tree_f64": (I32, [P, I32, P, I64, I32, I32, P]),
-    "afm_zpredict_f64": (I32, [P, P, I64, I64, I64, I64, P, I32, P, P, P, P]),
-    "afm_lasso_fit_f64": (I32, [P, P, P, I32, DBL, I32, DBL, I32, P, P]),
-    "afm_lasso_batch_f64": (I32, [P, P, I64, P, I64, I32, P, I32, I64, I32, I32, DBL, I32, P, P]),
-    "afm_gram_score_f64": (I32, [P, P, I64, P, I64, I32, P, I32, I64, P]),
+    "afm_ctx_create": ("status", "int ptr"),
+    "afm_ctx_set_stream": ("status", "ctx ptr"),
+    "afm_ctx_set_option": ("status", "ctx str i64"),
+    "afm_ctx_get_option": ("status", "ctx str host:i64*"),
+    "afm_stream_create_cu_mask": ("status", "int ptr int ptr"),
+    "afm_stream_destroy": ("status", "ptr"),
+    "afm_ctx_destroy": ("status", "ctx"),
+    "afm_last_error": ("str", ""),
+    "afm_version": ("int", ""),
+    "afm_factor_name": ("str", "int"),
+    "afm_factors_f64": ("status", "ctx i64 i64 i64 f64* f64* f64* f64* i64* f64* i64* i64*"),
+    "afm_factors_state_bytes": ("i64", "ctx i64"),
+    "afm_factors_slab_f64": ("status", "ctx i64 i64 i64 i64 i64 f64* f64* f64* f64* i64* f64* i64* "
+                                       "i64* f64*"),
+    "afm_factors_range_f64": ("status", "ctx i64 i64 i64 i64 i64 f64* f64* f64* f64* i64* f64* "
+                                        "i64* i64* f64*"),
+    "afm_xs_gram_f64": ("status", "ctx f64* i64 i64 i64 i64 i32* int int i64* i64 i64 f64* f64*"),
+    "afm_ols_solve_f64": ("status", "ctx f64* f64* int i64 f64 f64* f64* i32*"),
+    "afm_pool_moments_f64": ("status", "ctx f64* f64* int i64 f64* f64*"),
+    "afm_pool_tree_f64": ("status", "ctx f64* f64* int i64 int f64* f64*"),
+    "afm_pool_segments_f64": ("status", "ctx f64* f64* int i64 i64 f64* f64*"),
+    "afm_labels_f64": ("status", "ctx i64 i64 i64 i64 f64* f64* i64* f64* f64*"),
+    "afm_drop_last_obs_bits": ("status", "ctx i64 i64 i64* i64* i64*"),
+    "afm_drop_last_obs_bits_range": ("status", "ctx i64 i64 i64* i64* i64* i64 i64"),
+    "afm_factors_part_words": ("i64", "ctx i64 i64 i64 i64"),
+    "afm_factors_range_part_f64": ("status", "ctx i64 i64 i64 i64 i64 f64* f64* i64* f64* f64* "
+                                             "i64*"),
+    "afm_factor_masks_f64": ("status", "ctx i64 i64 i64 i64 i64 i64* i64* i64* i64*"),
+    "afm_predict_f64": ("status", "ctx f64* i64 i64 i64 i64 i32* int f64* i64 i64* int f64*"),
+    "afm_fama_macbeth_f64": ("status", "ctx f64* i32* i64 int f64* f64*"),
+    "afm_ols_residual_f64": ("status", "ctx f64* i64 int int f64* f64* f64*"),
+    "afm_vec_add_f64": ("status", "ctx i64 f64* f64*"),
+    "afm_ols_intercept_f64": ("status", "ctx int f64* f64*"),
+    "afm_lasso_cd_f64": ("status", "ctx f64* int f64 f64 int f64 int f64* f64*"),
+    "afm_talib_factors_f64": ("status", "ctx i64 i64 i64 f64* f64* i64* f64*"),
+    "afm_ffill_f64": ("status", "ctx i64 i64 i64 f64* i64*"),
+    "afm_date_mean_fill_f64": ("status", "ctx i64 i64 i64 i64 f64* i64* f64*"),
+    "afm_group_demean_f64": ("status", "ctx i64 i64* i64 f64* f64* f64*"),
+    "afm_rebalance_f64": ("status", "ctx i64 i64 i64 i32* i64 f64* i64* f64* i64* i64 i64 i64 f64* "
+                                    "f64* int f64 f64 i32* i32* f64* f64* i32* i64* i32*"),
+    "afm_pnl_scan_f64": ("status", "ctx i64 i32* i32* f64* i32* i64* f64 f64 f64* f64* f64* f64*"),
+    "afm_bootstrap_pnl_f64": ("status", "ctx i64 i32* i64 f64* i32* i32* f64* i64 i64 i32* f64 f64 "
+                                        "f64* f64* f64* f64*"),
+    "afm_min_variance_weights_f64": ("status", "ctx f64* i64 i64 int f64 f64 f64* f64* i32*"),
+    "afm_fwd_returns_f64": ("status", "ctx i64 i64 f64* i64* f64*"),
+    "afm_xs_prepare_f64": ("status", "ctx i64 i64 i64 f64* f64* f64* f64* i32* i32*"),
+    "afm_xs_prepare_range_f64": ("status", "ctx i64 i64 i64 i64 i64 f64* f64* f64* f64* i32* i32*"),
+    "afm_xs_rank_f64": ("status", "ctx i64 i64 f64* i32* i64* i32* i32* i32*"),
+    "afm_xs_layers_f64": ("status", "ctx i64 i64 f64* i32* i64* i32* i32* i32*"),
+    "afm_xs_stats_f64": ("status", "ctx i64 i64 i32* i64 f64* i32* i32* i32* int f64* f64* i32* "
+                                   "f64*"),
+    "afm_xs_series_f64": ("status", "ctx i64 f64* f64* f64* i32* int int f64* f64* f64* f64* f64*"),
+    "afm_zscore_stats_f64": ("status", "ctx f64* i64 i64 i64 i32* int i64* i64 i64 f64* f64*"),
+    "afm_zscore_stats_slab_f64": ("status", "ctx f64* i64 i64 i64 i32* int i64* i64 i64 f64* int "
+                                            "int f64* f64*"),
+    "afm_zscore_apply_f64": ("status", "ctx f64* i64 i64 i64 i32* int i64* i64 i64 f64* f64* f64* "
+                                       "i64 i32* i64*"),
+    "afm_zgram_part_bytes": ("int", "int"),
+    "afm_zstats_finalize_f64": ("status", "ctx f64* f64* int i64 f64* i32*"),
+    "afm_row_bits": ("status", "ctx i64 i64 i64* i64* i32* i64 i64 i64*"),
+    "afm_zgram_f64": ("status", "ctx f64* i64 i64 i32* i32* int int f64* int i64* i64 i64 int i64 "
+                                "i64 i64 f64* int"),
+    "afm_zpool_f64": ("status", "ctx f64* i64 i64 i32* i32* int int f64* int i64* i64 i64 i64 int "
+                                "i64 int f64* int"),
+    "afm_gram_tree_f64": ("status", "ctx int f64* i64 int int f64*"),
+    "afm_zpredict_f64": ("status", "ctx f64* i64 i64 i64 i64 i32* int f64* f64* i64* f64*"),
+    "afm_lasso_fit_f64": ("status", "ctx f64* f64* int f64 int f64 int f64* f64*"),
+    "afm_lasso_batch_f64": ("status", "ctx f64* i64 f64* i64 int f64* int i64 int int f64 int f64* "
+                                      "f64*"),
+    "afm_gram_score_f64": ("status", "ctx f64* i64 f64* i64 int f64* int i64 f64*"),
 }
+_RESTYPE = {"status": I32, "int": I32, "i64": I64, "str": ctypes.c_char_p}
+_ARGTYPE = {"int": I32, "i64": I64, "f64": DBL, "str": ctypes.c_char_p}    # every pointer: void*
 
 
 class AfmError(RuntimeError):
@@ -106,10 +119,10 @@ def lib():
                     raise ImportError(f"{LIB_PATH} is not built: run `make -C "
                                       f"{os.path.dirname(HERE)}` (hipcc, gfx950)")
                 L = ctypes.CDLL(LIB_PATH)
-                for name, (res, args) in SIGNATURES.items():
+                for name, (res, params) in SIGNATURES.items():
                     f = getattr(L, name)
-                    f.restype = res
-                    f.argtypes = args
+                    f.restype = _RESTYPE[res]
+                    f.argtypes = [_ARGTYPE.get(t, P) for t in params.split()]
                 _lib = L
     return _lib
 
@@ -118,6 +131,46 @@ def check(rc: int, what: str = ""):
     if rc != 0:
         msg = lib().afm_last_error().decode(errors="replace")
         raise AfmError(f"{what or 'afm'} failed ({rc}): {msg}")
+
+
+def _as_given(a):
+    return a
+
+
+def _device_buffer(dtype, device: int, where: str):
+    """Converter of one f64* / i32* / i64* parameter: None -> NULL, a contiguous ``dtype`` tensor
+    on cuda:``device`` -> its address; anything else is rejected before the library is entered."""
+    import torch
+
+    def conv(t):
+        if t is None:
+            return None
+        if not isinstance(t, torch.Tensor):
+            raise AfmError(f"{where}: expected a {dtype} tensor or None, got {type(t).__name__}")
+        if t.get_device() != device or t.dtype is not dtype or not t.is_contiguous():
+            raise AfmError(f"{where}: expected a contiguous {dtype} tensor on cuda:{device}, got "
+                           f"{t.dtype} on {t.device}, contiguous={t.is_contiguous()}")
+        return t.data_ptr()
+    return conv
+
+
+def _plans(device: int) -> dict:
+    """name -> (takes the context, one converter per further parameter, failed(return value)):
+    how Context.call marshals each entry point of SIGNATURES for the context of ``device``."""
+    import torch
+    scalar = {"int": operator.index, "i64": operator.index, "f64": float}
+    buffer = {"f64*": torch.float64, "i32*": torch.int32, "i64*": torch.int64}
+    negative = (0).__gt__
+    failed = {"status": bool, "int": negative, "i64": negative, "str": lambda s: s is None}
+    plans = {}
+    for name, (res, params) in SIGNATURES.items():
+        toks = params.split()
+        takes_ctx = toks[:1] == ["ctx"]
+        convs = tuple(_device_buffer(buffer[t], device, f"{name} argument {i}") if t in buffer
+                      else scalar.get(t, _as_given)
+                      for i, t in enumerate(toks[takes_ctx:], 1))
+        plans[name] = (takes_ctx, convs, failed[res])
+    return plans
 
 
 class Context:
@@ -130,6 +183,26 @@ class Context:
         h = P()
         check(lib().afm_ctx_create(device, ctypes.byref(h)), "afm_ctx_create")
         self.handle = h
+        self._plans = _plans(device)
+
+    def call(self, name: str, *args):
+        """The entry point ``name`` of the library (looked up at call time) with this context's
+        handle first where it takes one, ``args`` marshalled by its SIGNATURES entry: a device
+        buffer parameter takes a tensor (checked: device, dtype, contiguity) or None, an integer
+        parameter anything with ``__index__``, a double anything ``float()`` takes, an opaque
+        pointer a c_void_p / ctypes array / int.  Raises AfmError on a failure return (a status
+        that is not 0, a negative count), else returns the value.  The stream is the caller's
+        business: ``on`` inside a pipeline, ``run`` for a stand-alone launch."""
+        takes_ctx, convs, failed = self._plans[name]
+        if len(args) != len(convs):
+            raise TypeError(f"{name} takes {len(convs)} arguments ({len(args)} given)")
+        cargs = [cv(a) for cv, a in zip(convs, args)]
+        fn = getattr(lib(), name)
+        rc = fn(self.handle, *cargs) if takes_ctx else fn(*cargs)
+        if failed(rc):
+            raise AfmError(f"{name} failed ({rc}): "
+                           f"{lib().afm_last_error().decode(errors='replace')}")
+        return rc
 
     @classmethod
     def get(cls, device: int | None = None) -> "Context":
@@ -145,14 +218,12 @@ class Context:
 
     def set_option(self, name: str, value: int):
         """afm_ctx_set_option: an execution option of this context (include/afm.h)."""
-        check(lib().afm_ctx_set_option(self.handle, name.encode(), int(value)),
-              f"afm_ctx_set_option({name})")
+        self.call("afm_ctx_set_option", name.encode(), int(value))
 
     def get_option(self, name: str) -> int:
         """afm_ctx_get_option: the current value of an execution option."""
         v = I64()
-        check(lib().afm_ctx_get_option(self.handle, name.encode(), ctypes.byref(v)),
-              f"afm_ctx_get_option({name})")
+        self.call("afm_ctx_get_option", name.encode(), ctypes.byref(v))
         return int(v.value)
 
     def bind_stream(self):
@@ -179,6 +250,16 @@ def ptr(t) -> P:
     if not t.is_contiguous():
         raise AfmError("tensor must be contiguous")
     return P(t.data_ptr())
+
+
+def run(name: str, *args, device: int | None = None):
+    """A stand-alone launch: ``Context.call`` on the context of ``device`` (default: the device of
+    the first tensor among ``args``), bound to torch's current stream of that device."""
+    if device is None:
+        device = next((a.device.index for a in args if hasattr(a, "data_ptr")), None)
+    ctx = Context.get(device)
+    ctx.bind_stream()
+    return ctx.call(name, *args)
 
 
 def factor_names() -> list:

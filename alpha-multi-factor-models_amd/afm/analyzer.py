@@ -31,23 +31,20 @@ def evaluate_grid(sig, close, price_bits, *, A: int, dates_idx=None, year=None):
     T, lda = sig.shape
     plane = T * lda
     ctx = _lib.Context.get(dev.index)
-    P = _lib.ptr
-    L = _lib.lib()
-    h = ctx.bind_stream()
+    ctx.bind_stream()
+    call = ctx.call
     fr = torch.empty((3, T, lda), dtype=torch.float64, device=dev)
-    _lib.check(L.afm_fwd_returns_f64(h, T, lda, P(close), P(price_bits), P(fr)), "fwd_returns")
+    call("afm_fwd_returns_f64", T, lda, close, price_bits, fr)
     scratch = torch.empty((T, lda), dtype=torch.float64, device=dev)
     rows = torch.empty((4, T, lda), dtype=torch.float64, device=dev)
     rows_idx = torch.empty((T, lda), dtype=torch.int32, device=dev)
     nrows = torch.empty(T, dtype=torch.int32, device=dev)
-    _lib.check(L.afm_xs_prepare_f64(h, T, A, lda, P(sig), P(fr), P(scratch), P(rows), P(rows_idx),
-                                    P(nrows)), "xs_prepare")
+    call("afm_xs_prepare_f64", T, A, lda, sig, fr, scratch, rows, rows_idx, nrows)
     skey = torch.empty((T, lda), dtype=torch.int64, device=dev)
     sidx = torch.empty((T, lda), dtype=torch.int32, device=dev)
     ra = torch.empty((T, lda), dtype=torch.int32, device=dev)
     rd = torch.empty((T, lda), dtype=torch.int32, device=dev)
-    _lib.check(L.afm_xs_rank_f64(h, T, lda, P(rows), P(nrows), P(skey), P(sidx), P(ra), P(rd)),
-               "xs_rank")
+    call("afm_xs_rank_f64", T, lda, rows, nrows, skey, sidx, ra, rd)
     nr = nrows.cpu().numpy()
     if dates_idx is None:
         dates_idx = np.flatnonzero(nr > 0).astype(np.int32)
@@ -58,8 +55,7 @@ def evaluate_grid(sig, close, price_bits, *, A: int, dates_idx=None, year=None):
     lm = torch.empty((nd, 3, 10), dtype=torch.float64, device=dev)
     lc = torch.empty((nd, 10), dtype=torch.int32, device=dev)
     port = torch.empty((nd, 3), dtype=torch.float64, device=dev)
-    _lib.check(L.afm_xs_stats_f64(h, T, lda, P(d_t), nd, P(rows), P(nrows), P(ra), P(rd), mcols,
-                                  P(ic), P(lm), P(lc), P(port)), "xs_stats")
+    call("afm_xs_stats_f64", T, lda, d_t, nd, rows, nrows, ra, rd, mcols, ic, lm, lc, port)
     out = {"fr": fr, "rows": rows, "rows_idx": rows_idx, "nrows": nrows, "rank_asc": ra,
            "rank_desc": rd, "dates_idx": dates_idx, "ic": ic, "layer_mean": lm,
            "layer_cnt": lc, "port": port, "mcols": mcols}
@@ -72,9 +68,7 @@ def evaluate_grid(sig, close, price_bits, *, A: int, dates_idx=None, year=None):
         cum_port = torch.empty_like(port)
         ir = torch.empty((ny, 3), dtype=torch.float64, device=dev)
         scr = torch.empty((3 * ny, nd), dtype=torch.float64, device=dev)
-        _lib.check(L.afm_xs_series_f64(h, nd, P(lm), P(port), P(ic), P(y_t), ny, y0,
-                                       P(cum_layer), P(ls), P(cum_port), P(ir), P(scr)),
-                   "xs_series")
+        call("afm_xs_series_f64", nd, lm, port, ic, y_t, ny, y0, cum_layer, ls, cum_port, ir, scr)
         out.update(cum_layer=cum_layer, ls=ls, cum_port=cum_port, ir=ir, year0=y0, years=yr)
     return out
 

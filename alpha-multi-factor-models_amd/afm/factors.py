@@ -49,11 +49,9 @@ def factor_panel(grid: PanelGrid, out=None, nanfree=None, finite=None):
         nanfree = torch.zeros(((T + 63) // 64, lda), dtype=torch.int64, device=grid.device)
     assert out.shape == (N_FACTORS, T, lda) and out.dtype == torch.float64
     assert nanfree.shape == ((T + 63) // 64, lda)
-    P = _lib.ptr
-    _lib.check(_lib.lib().afm_factors_f64(
-        ctx.bind_stream(), T, grid.A, lda, P(grid.close), P(grid.volume), P(grid.ret1d),
-        P(grid.excess), P(grid.vbits), P(out), P(nanfree),
-        P(finite) if finite is not None else None), "afm_factors_f64")
+    ctx.bind_stream()
+    ctx.call("afm_factors_f64", T, grid.A, lda, grid.close, grid.volume, grid.ret1d, grid.excess,
+             grid.vbits, out, nanfree, finite)
     return out, nanfree
 
 

@@ -65,11 +65,9 @@ def fill_panel(values: np.ndarray, t_idx: np.ndarray, a_idx: np.ndarray, T: int,
     bits = pack_bits(valid)
     scratch = torch.empty_like(planes)
     ctx = _lib.Context.get(dev.index)
-    h = ctx.bind_stream()
-    L, P = _lib.lib(), _lib.ptr
-    _lib.check(L.afm_ffill_f64(h, K, T, lda, P(planes), P(bits)), "afm_ffill_f64")
-    _lib.check(L.afm_date_mean_fill_f64(h, K, T, A, lda, P(planes), P(bits), P(scratch)),
-               "afm_date_mean_fill_f64")
+    ctx.bind_stream()
+    ctx.call("afm_ffill_f64", K, T, lda, planes, bits)
+    ctx.call("afm_date_mean_fill_f64", K, T, A, lda, planes, bits, scratch)
     return planes[:, ti, ai].T.contiguous().cpu().numpy()
 
 
@@ -84,11 +82,8 @@ def group_demean(x: np.ndarray, offsets: np.ndarray, device=None) -> np.ndarray:
     off = torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.int64)).to(dev)
     out = torch.empty_like(xt)
     scratch = torch.empty_like(xt)
-    ctx = _lib.Context.get(dev.index)
-    _lib.check(_lib.lib().afm_group_demean_f64(ctx.bind_stream(), len(offsets) - 1, _lib.ptr(off),
-                                               int(np.diff(offsets).max()), _lib.ptr(xt),
-                                               _lib.ptr(out), _lib.ptr(scratch)),
-               "afm_group_demean_f64")
+    _lib.run("afm_group_demean_f64", len(offsets) - 1, off, int(np.diff(offsets).max()), xt, out,
+             scratch)
     return out.cpu().numpy()
 
 

@@ -176,12 +176,7 @@ def factor_panel_slabs(grid: PanelGrid, consumer, bars_per_slab: int | None = No
     step = int(bars_per_slab) if bars_per_slab is not None else slab_bars(grid)
     if step <= 0 or step % 64:
         raise ValueError("bars_per_slab must be a positive multiple of 64")
-    ctx = _lib.Context.get(grid.device.index)
-    L, P = _lib.lib(), _lib.ptr
-    h = ctx.bind_stream()
-    nbytes = int(L.afm_factors_state_bytes(h, grid.A))
-    if nbytes < 0:
-        raise RuntimeError("afm_factors_state_bytes failed")
+    nbytes = _lib.run("afm_factors_state_bytes", grid.A, device=grid.device.index)
     state = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=grid.device)
     out = torch.empty((N_FACTORS, min(step, T), lda), dtype=torch.float64, device=grid.device)
     nanfree = torch.empty(((min(step, T) + 63) // 64, lda), dtype=torch.int64, device=grid.device)
@@ -192,10 +187,8 @@ def factor_panel_slabs(grid: PanelGrid, consumer, bars_per_slab: int | None = No
         o = out if m == out.shape[1] else out.view(-1)[: N_FACTORS * m * lda].view(N_FACTORS, m, lda)
         nw = (m + 63) // 64
         nf = nanfree if nw == nanfree.shape[0] else nanfree[:nw]
-        _lib.check(L.afm_factors_slab_f64(ctx.bind_stream(), T, grid.A, lda, t0, t1,
-                                          P(grid.close), P(grid.volume), P(grid.ret1d),
-                                          P(grid.excess), P(grid.vbits), P(o), P(nf), None,
-                                          P(state)), "afm_factors_slab_f64")
+        _lib.run("afm_factors_slab_f64", T, grid.A, lda, t0, t1, grid.close, grid.volume,
+                 grid.ret1d, grid.excess, grid.vbits, o, nf, None, state)
         consumer(t0, t1, o, nf)
         n += 1
     return n

@@ -201,8 +201,8 @@ class Pipeline:
     one device, so every result is bit-identical to N = 1.
 
     Streams: a step runs on ``main``, side work forked onto ``side`` / ``side2`` / ``side3``.  Every
-    switch of stream is a ``with self.ctx.on(stream) as h:`` scope (torch's current stream and the
-    afm context move and are restored together); a helper that launches takes the scope's ``h``."""
+    switch of stream is a ``with self.ctx.on(stream):`` scope (torch's current stream and the afm
+    context move and are restored together); every launch in it is a ``self.ctx.call``."""
 
     def __init__(self, grid: PanelGrid, cfg: PipelineConfig | None = None, comm=None):
         import torch
@@ -211,6 +211,7 @@ class Pipeline:
         self.W = W = comm.world if comm is not None else 1
         self.rank = comm.rank if comm is not None else 0
         self.cfg = c = cfg or PipelineConfig()
+        self.ctx = _lib.Context.get(grid.device.index)
         T, lda, A = grid.T, grid.lda, grid.A
         self.T, self.lda, self.A, self.nch = T, lda, A, (T + 63) // 64
         self.sp = Split.of(grid.dates, c.train_end, c.valid_end)
@@ -274,7 +275,7 @@ class Pipeline:
         self.sd = torch.empty((p, lda_r), **f64)
         self.zs = torch.empty((p + 1, lda_r, 2), **f64)
         self.asset_ok = torch.empty(lda_r, **i32)
-        self.pe = pe = _lib.lib().afm_zgram_part_bytes(p) // 8
+        self.pe = pe = self.ctx.call("afm_zgram_part_bytes", p) // 8
         self.pool_part = torch.empty((nrb, N_CHUNKS, pe), **f64)
         self.pool_c1 = torch.empty((nrb * (N_CHUNKS // CHUNK_TREE[0]), pe), **f64)
         self.pool_rb = torch.empty((nrb, pe), **f64)
@@ -295,7 +296,7 @@ class Pipeline:
         T, W, pf = self.T, self.W, self.pf
         self.fm_cols = torch.as_tensor(np.array([COL[n] for n in self.cfg.fm_features], np.int32),
                                        device=self.full.device)
-        self.pef = pef = _lib.lib().afm_zgram_part_bytes(pf) // 8
+        self.pef = pef = self.ctx.call("afm_zgram_part_bytes", pf) // 8
         self.fm_part = torch.zeros((T, self.nblk_r, pef), **f64)
         self.fm_sub = torch.zeros((T, pef), **f64)      # this shard's subtree per date
         self.fdr = [even_range(T, W, q) for q in range(W)]   # FM dates owned by each rank
@@ -406,10 +407,9 @@ class Pipeline:
         self.an_rng = self.an_ranges[self.rank]
 
     def _init_streams(self):
-        """The afm context and the step's streams, created in the order main, side, side2, side3."""
+        """The step's streams, created in the order main, side, side2, side3."""
         import torch
         c, W, dev = self.cfg, self.W, self.full.device
-        self.ctx = _lib.Context.get(dev.index)
         if c.fm_fork not in ("gram", "predict", "analyzer", "rebalance"):
             raise ValueError(f"fm_fork={c.fm_fork!r}: expected gram, predict, analyzer or "
                              "rebalance")
@@ -438,7 +438,7 @@ class Pipeline:
         """The time slabs of the streamed / early factor stages: bounds, carried state, events."""
         import torch
         f64, i64, _ = self._opts
-        L, c, sp, T, A_r, lda_r = _lib.lib(), self.cfg, self.sp, self.T, self.A_r, self.lda_r
+        c, sp, T, A_r, lda_r = self.cfg, self.sp, self.T, self.A_r, self.lda_r
         # early z statistics: the first slab ends at the first 64-date boundary past the train
         # window (the slab API's alignment)
         self.ta = min(((sp.tr1 + 63) // 64) * 64, T)
@@ -450,13 +450,12 @@ class Pipeline:
             self.zbounds = bounds = sorted({0, T} | {min(T, ((i * T // nslab + 63) // 64) * 64)
                                                      for i in range(1, nslab)})
             self.zstate = torch.empty((5, self.p, lda_r), **f64)
-            self.zparts = [torch.empty(int(L.afm_factors_part_words(self.ctx.handle, A_r, lda_r,
-                                                                    a, z)), **i64)
-                           for a, z in zip(bounds[:-1], bounds[1:])]
+            self.zparts = [torch.empty(self.ctx.call("afm_factors_part_words", A_r, lda_r, a, z),
+                                       **i64) for a, z in zip(bounds[:-1], bounds[1:])]
             self.zslab_done = [torch.cuda.Event() for _ in bounds[:-1]]
         self.early = (bool(c.early_zstats) and not self.stream_z and A_r > 0 and self.ta < T)
         if self.early or self.stream_z:
-            nb = int(L.afm_factors_state_bytes(self.ctx.handle, A_r))
+            nb = self.ctx.call("afm_factors_state_bytes", A_r)
             self.fstate = torch.empty(nb // 8 + 1, **f64)
             self.slab1_done = torch.cuda.Event()
             self.zstats_done = torch.cuda.Event()
@@ -477,125 +476,105 @@ class Pipeline:
         panel, or (``full``, N > 1) the full-width planes the rebalance reads."""
         g, lda, t0, tgt, tmr = ((self.full, self.lda, self.lab0, self.target, self.tmr) if full
                                 else (self.g, self.lda_r, 0, self.out[TARGET], self.out[TMR]))
-        P = _lib.ptr
-        with self.ctx.on(stream) as h:
-            _lib.check(_lib.lib().afm_labels_f64(h, self.T, lda, t0, self.T, P(g.excess),
-                                                 P(g.ret1d), P(g.vbits), P(tgt), P(tmr)), "labels")
+        with self.ctx.on(stream):
+            self.ctx.call("afm_labels_f64", self.T, lda, t0, self.T, g.excess, g.ret1d, g.vbits,
+                          tgt, tmr)
             self.labels_done.record(stream)
 
-    def _last_obs_rows(self, h, t0=None, t1=None):
+    def _last_obs_rows(self, t0=None, t1=None):
         """nanfree -> all_df rows and finite -> frows (an asset's last observation dropped), of
         every date or of the dates [t0, t1)."""
-        L, P = _lib.lib(), _lib.ptr
-        fn, rng = ((L.afm_drop_last_obs_bits, ()) if t0 is None
-                   else (L.afm_drop_last_obs_bits_range, (t0, t1)))
+        fn, rng = (("afm_drop_last_obs_bits", ()) if t0 is None
+                   else ("afm_drop_last_obs_bits_range", (t0, t1)))
         for src, dst in ((self.nanfree, self.alldf), (self.finite, self.frows)):
-            _lib.check(fn(h, self.T, self.lda_r, P(self.g.vbits), P(src), P(dst), *rng),
-                       "last-obs rows")
+            self.ctx.call(fn, self.T, self.lda_r, self.g.vbits, src, dst, *rng)
 
-    def _zrows(self, h, w0, nw, nt):
+    def _zrows(self, w0, nw, nt):
         """The z-score rows (frows of the surviving assets) of the ``nw`` 64-date words from
         ``w0`` on, ``nt`` dates."""
-        P = _lib.ptr
-        _lib.check(_lib.lib().afm_row_bits(h, nw, self.lda_r, P(self.frows[w0:]), None,
-                                           P(self.asset_ok), 0, nt, P(self.zrows[w0:])), "z rows")
+        self.ctx.call("afm_row_bits", nw, self.lda_r, self.frows[w0:], None, self.asset_ok, 0, nt,
+                      self.zrows[w0:])
 
-    def _zstats(self, h, nw, nt):
+    def _zstats(self, nw, nt):
         """The train window's z statistics, the surviving assets, and the z-score rows of the
         first ``nw`` words (``nt`` dates)."""
-        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
-        T, lda_r, p = self.T, self.lda_r, self.p
-        chk(L.afm_zscore_stats_f64(h, P(self.out), T * lda_r, T, lda_r, P(self.feat), p,
-                                   P(self.alldf), 0, self.sp.tr1, P(self.mu), P(self.sd)),
-            "zscore stats")
-        chk(L.afm_zstats_finalize_f64(h, P(self.mu), P(self.sd), p, lda_r, P(self.zs),
-                                      P(self.asset_ok)), "zstats finalize")
-        self._zrows(h, 0, nw, nt)
+        call, T, lda_r, p = self.ctx.call, self.T, self.lda_r, self.p
+        call("afm_zscore_stats_f64", self.out, T * lda_r, T, lda_r, self.feat, p, self.alldf, 0,
+             self.sp.tr1, self.mu, self.sd)
+        call("afm_zstats_finalize_f64", self.mu, self.sd, p, lda_r, self.zs, self.asset_ok)
+        self._zrows(0, nw, nt)
 
-    def _pooled_blocks(self, h, t0, nt, bufs=None, mark=None):
+    def _pooled_blocks(self, t0, nt, bufs=None, mark=None):
         """This shard's pooled-Gram block results (rows of the dates [t0, t0 + nt)): row-block x
         chunk partials, then the tree -- the chunks of a row-block (32, then 2), the row-blocks
         of an asset block -> pool_blk[0:nblk_r], or in the buffers ``bufs`` (part, c1, rb, blk)
         instead of the step's."""
-        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
-        T, lda, p = self.T, self.lda_r, self.p
+        call, T, lda, p = self.ctx.call, self.T, self.lda_r, self.p
         part, c1b, rb, blk = bufs or (self.pool_part, self.pool_c1, self.pool_rb, self.pool_blk)
         blk.zero_()
         if self.nrb == 0:
             return
         if mark is not None:
             mark("k_gram", 0)
-        chk(L.afm_zpool_f64(h, P(self.out), T * lda, lda, P(self.feat), None, p, TARGET,
-                            P(self.zs), p, P(self.zrows), t0, nt, 0, self.nrb, self.A_r,
-                            N_CHUNKS, P(part), 0), "zpool")
+        call("afm_zpool_f64", self.out, T * lda, lda, self.feat, None, p, TARGET, self.zs, p,
+             self.zrows, t0, nt, 0, self.nrb, self.A_r, N_CHUNKS, part, 0)
         if mark is not None:
             mark("k_gram", 1)
         c1, c2 = CHUNK_TREE
-        chk(L.afm_gram_tree_f64(h, p, P(part), self.nrb * N_CHUNKS, c1, 0, P(c1b)), "tree chunks")
-        chk(L.afm_gram_tree_f64(h, p, P(c1b), self.nrb * c2, c2, 0, P(rb)), "tree chunks 2")
-        chk(L.afm_gram_tree_f64(h, p, P(rb), self.nrb, self.rb_per_blk, 0, P(blk)),
-            "tree row-blocks")
+        call("afm_gram_tree_f64", p, part, self.nrb * N_CHUNKS, c1, 0, c1b)
+        call("afm_gram_tree_f64", p, c1b, self.nrb * c2, c2, 0, rb)
+        call("afm_gram_tree_f64", p, rb, self.nrb, self.rb_per_blk, 0, blk)
 
-    def _te_subtree(self, h, t):
+    def _te_subtree(self, t):
         """This shard's subtree of the train_end date's Gram -> pool_blk[nblk_r]."""
-        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
-        T, lda, p = self.T, self.lda_r, self.p
+        call, T, lda, p = self.ctx.call, self.T, self.lda_r, self.p
         if self.nrb == 0:
             return
-        chk(L.afm_zgram_f64(h, P(self.out), T * lda, lda, P(self.feat), None, p, TARGET,
-                            P(self.zs), p, P(self.zrows), t, 1, self.nblk_r, 0, self.blk,
-                            self.A_r, P(self.te_part), 0), "zgram date")
-        chk(L.afm_gram_tree_f64(h, p, P(self.te_part), self.nblk_r, self.nblk_r, 0,
-                                P(self.pool_blk[self.nblk_r:])), "tree date")
+        call("afm_zgram_f64", self.out, T * lda, lda, self.feat, None, p, TARGET, self.zs, p,
+             self.zrows, t, 1, self.nblk_r, 0, self.blk, self.A_r, self.te_part, 0)
+        call("afm_gram_tree_f64", p, self.te_part, self.nblk_r, self.nblk_r, 0,
+             self.pool_blk[self.nblk_r:])
 
-    def _fm_local(self, h):
+    def _fm_local(self):
         """This shard's per-date FM30 partials over the z-score rows, merged over its blocks ->
         fm_sub [T]."""
-        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
-        T, lda, pf = self.T, self.lda_r, self.pf
+        call, T, lda, pf = self.ctx.call, self.T, self.lda_r, self.pf
         if self.nrb == 0:
             return
-        chk(L.afm_zgram_f64(h, P(self.out), T * lda, lda, P(self.fm_cols), None, pf, TARGET,
-                            None, 0, P(self.zrows), 0, T, self.nblk_r, 0, self.blk, self.A_r,
-                            P(self.fm_part), self.fm_grid), "zgram fm")
-        chk(L.afm_gram_tree_f64(h, pf, P(self.fm_part), T * self.nblk_r, self.nblk_r, 0,
-                                P(self.fm_sub)), "tree fm blocks")
+        call("afm_zgram_f64", self.out, T * lda, lda, self.fm_cols, None, pf, TARGET, None, 0,
+             self.zrows, 0, T, self.nblk_r, 0, self.blk, self.A_r, self.fm_part, self.fm_grid)
+        call("afm_gram_tree_f64", pf, self.fm_part, T * self.nblk_r, self.nblk_r, 0, self.fm_sub)
 
-    def _fm_solve(self, h, sub):
+    def _fm_solve(self, sub):
         """Owned dates: the rank subtrees ``sub`` [fnd][W][part] -> Grams, solves."""
-        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
-        pf = self.pf
+        call, pf = self.ctx.call, self.pf
         if self.fnd > 0:
-            chk(L.afm_gram_tree_f64(h, pf, P(sub), self.fnd * self.W, self.W, 1,
-                                    P(self.fm_gram)), "tree fm ranks")
-            chk(L.afm_ols_solve_f64(h, P(self.fm_gram), P(self.fm_shift), pf, self.fnd,
-                                    self.cfg.tol, P(self.fm_beta_own), P(self.fm_nobs_own),
-                                    P(self.fm_rank_own)), "fm solve")
+            call("afm_gram_tree_f64", pf, sub, self.fnd * self.W, self.W, 1, self.fm_gram)
+            call("afm_ols_solve_f64", self.fm_gram, self.fm_shift, pf, self.fnd, self.cfg.tol,
+                 self.fm_beta_own, self.fm_nobs_own, self.fm_rank_own)
 
-    def _fm_stats(self, h):
-        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
-        chk(L.afm_fama_macbeth_f64(h, P(self.fm_beta), P(self.fm_rank), self.T, self.pf + 1,
-                                   P(self.fm_mean), P(self.fm_t)), "fama_macbeth")
+    def _fm_stats(self):
+        self.ctx.call("afm_fama_macbeth_f64", self.fm_beta, self.fm_rank, self.T, self.pf + 1,
+                      self.fm_mean, self.fm_t)
 
     # ---- the factor stage's three paths --------------------------------------------------------
-    def _factors_one_pass(self, h, lab_side, mark):
+    def _factors_one_pass(self, lab_side, mark):
         """The factor panel in one call on the main stream, then the all_df rows.  One GPU: the
         two label planes on the second side stream, enqueued after the factor kernel (it runs
         on the CUs the factor workgroups leave free); the z statistics wait for them."""
-        L, P, g = _lib.lib(), _lib.ptr, self.g
+        g = self.g
         if self.A_r > 0:
             mark("k_factor", 0)
-            _lib.check(L.afm_factors_f64(h, self.T, self.A_r, self.lda_r, P(g.close), P(g.volume),
-                                         None if lab_side else P(g.ret1d),
-                                         None if lab_side else P(g.excess), P(g.vbits),
-                                         P(self.out), P(self.nanfree), P(self.finite)), "factors")
+            self.ctx.call("afm_factors_f64", self.T, self.A_r, self.lda_r, g.close, g.volume,
+                          None if lab_side else g.ret1d, None if lab_side else g.excess, g.vbits,
+                          self.out, self.nanfree, self.finite)
             mark("k_factor", 1)
             if lab_side:
                 self._labels(self.side2)
-            self._last_obs_rows(h)
+            self._last_obs_rows()
         mark("factors", 1)
 
-    def _factors_streamed(self, h, lab_side, mark):
+    def _factors_streamed(self, lab_side, mark):
         """The factor panel in time slabs (zbounds) on the main stream, each slab's all_df rows
         right behind it, and the train window's z statistics streamed slab by slab on the side
         stream as each slab lands (afm_zscore_stats_slab_f64, every (feature, asset) recurrence
@@ -604,77 +583,71 @@ class Pipeline:
         inside every factor slab; with ``labels_side`` off, on the main stream ahead of the first
         slab, inside the factors stage)."""
         import torch
-        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
-        g, T, lda_r, p, A_r = self.g, self.T, self.lda_r, self.p, self.A_r
+        call, g, T, lda_r, p, A_r = self.ctx.call, self.g, self.T, self.lda_r, self.p, self.A_r
         self._labels(self.side2 if lab_side else self.main)
         b, tr1 = self.zbounds, self.sp.tr1
         for i in range(len(b) - 1):
             t0, t1 = b[i], b[i + 1]
             # the slab on the main stream; its row masks, all_df rows and z statistics on the side
             # stream beside the next slab (the next slab needs only the carried factor state)
-            need = int(L.afm_factors_part_words(self.ctx.handle, A_r, lda_r, t0, t1))
+            need = call("afm_factors_part_words", A_r, lda_r, t0, t1)
             if need > self.zparts[i].numel():    # (an execution option changed the launch shape)
                 self.zparts[i] = torch.empty(need, dtype=torch.int64, device=self.out.device)
             part = self.zparts[i]
-            chk(L.afm_factors_range_part_f64(h, T, A_r, lda_r, t0, t1, P(g.close), P(g.volume),
-                                             P(g.vbits), P(self.out), P(self.fstate), P(part)),
-                "factors slab")
+            call("afm_factors_range_part_f64", T, A_r, lda_r, t0, t1, g.close, g.volume, g.vbits,
+                 self.out, self.fstate, part)
             self.zslab_done[i].record(self.main)
-            with self.ctx.on(self.side) as hs:
+            with self.ctx.on(self.side):
                 self.side.wait_event(self.zslab_done[i])
-                chk(L.afm_factor_masks_f64(hs, T, A_r, lda_r, t0, t1, P(g.vbits), P(part),
-                                           P(self.nanfree), P(self.finite)), "factor masks")
-                self._last_obs_rows(hs, t0, t1)
+                call("afm_factor_masks_f64", T, A_r, lda_r, t0, t1, g.vbits, part, self.nanfree,
+                     self.finite)
+                self._last_obs_rows(t0, t1)
                 if t0 < tr1:
                     if i == 0:
                         self.side.wait_event(self.labels_done)
                         mark("zstats", 0)
                     last = t1 >= tr1
-                    chk(L.afm_zscore_stats_slab_f64(hs, P(self.out), T * lda_r, T, lda_r,
-                                                    P(self.feat), p, P(self.alldf), t0,
-                                                    min(t1, tr1), P(self.zstate), int(i == 0),
-                                                    int(last), P(self.mu), P(self.sd)),
-                        "zscore stats slab")
+                    call("afm_zscore_stats_slab_f64", self.out, T * lda_r, T, lda_r, self.feat, p,
+                         self.alldf, t0, min(t1, tr1), self.zstate, int(i == 0), int(last),
+                         self.mu, self.sd)
                     if last:
-                        chk(L.afm_zstats_finalize_f64(hs, P(self.mu), P(self.sd), p, lda_r,
-                                                      P(self.zs), P(self.asset_ok)),
-                            "zstats finalize")
+                        call("afm_zstats_finalize_f64", self.mu, self.sd, p, lda_r, self.zs,
+                             self.asset_ok)
                         mark("zstats", 1)
         mark("factors", 1)
         self.zstats_done.record(self.side)        # every slab's masks, rows and statistics
         self.main.wait_event(self.zstats_done)
-        self._zrows(h, 0, self.nch, T)
+        self._zrows(0, self.nch, T)
 
-    def _factors_early(self, h, lab_side, mark):
+    def _factors_early(self, lab_side, mark):
         """The factor panel in two slabs [0, ta) and [ta, T) on the main stream; the train
         window's z statistics (and the z-score row bits of the first slab) on the side stream
         beside the second slab.  Bitwise the same panel, statistics and row sets as one call."""
-        L, P, g, T, ta, wa = _lib.lib(), _lib.ptr, self.g, self.T, self.ta, self.ta // 64
-        lab = (None, None) if lab_side else (P(g.ret1d), P(g.excess))
+        g, T, ta, wa = self.g, self.T, self.ta, self.ta // 64
+        lab = (None, None) if lab_side else (g.ret1d, g.excess)
 
         def slab(t0, t1):
-            _lib.check(L.afm_factors_range_f64(h, T, self.A_r, self.lda_r, t0, t1, P(g.close),
-                                               P(g.volume), *lab, P(g.vbits), P(self.out),
-                                               P(self.nanfree), P(self.finite), P(self.fstate)),
-                       "factors slab")
+            self.ctx.call("afm_factors_range_f64", T, self.A_r, self.lda_r, t0, t1, g.close,
+                          g.volume, *lab, g.vbits, self.out, self.nanfree, self.finite,
+                          self.fstate)
         slab(0, ta)
         if lab_side:
             self._labels(self.side2)
-        self._last_obs_rows(h, 0, ta)
+        self._last_obs_rows(0, ta)
         self.slab1_done.record(self.main)
-        with self.ctx.on(self.side) as hs:
+        with self.ctx.on(self.side):
             self.side.wait_event(self.slab1_done)
             if lab_side:
                 self.side.wait_event(self.labels_done)          # tmr_ret1d is a feature
             mark("zstats", 0)
-            self._zstats(hs, wa, ta)
+            self._zstats(wa, ta)
             mark("zstats", 1)
             self.zstats_done.record(self.side)
         slab(ta, T)
-        self._last_obs_rows(h, ta, T)
+        self._last_obs_rows(ta, T)
         mark("factors", 1)
         self.main.wait_event(self.zstats_done)
-        self._zrows(h, wa, self.nch - wa, T - ta)
+        self._zrows(wa, self.nch - wa, T - ta)
 
     # ---- the step ------------------------------------------------------------------------------
     def step(self, events: dict | None = None):
@@ -688,36 +661,36 @@ class Pipeline:
             if events is not None and stage in events:
                 events[stage][which].record()
 
-        with self.ctx.on(self.main) as h:
-            self._stage_factors(h, mark)
-            self._stage_gram(h, mark)
-            self._stage_fit_predict(h, mark)
-            self._stage_tail(h, mark)
+        with self.ctx.on(self.main):
+            self._stage_factors(mark)
+            self._stage_gram(mark)
+            self._stage_fit_predict(mark)
+            self._stage_tail(mark)
         for s in self.streams:
             caller.wait_stream(s)
 
-    def _stage_factors(self, h, mark):
+    def _stage_factors(self, mark):
         """factors + zstats: the panel, the row sets and the train window's z statistics; the
         prediction-independent side work (label planes, the analyzer's forward returns) forked."""
         W, one_pass = self.W, not (self.early or self.stream_z)
         lab_side = W == 1 and self.cfg.labels_side
         mark("factors", 0)
         if self.stream_z:
-            self._factors_streamed(h, lab_side, mark)
+            self._factors_streamed(lab_side, mark)
         elif self.early:
-            self._factors_early(h, lab_side, mark)
+            self._factors_early(lab_side, mark)
         else:
-            self._factors_one_pass(h, lab_side, mark)
+            self._factors_one_pass(lab_side, mark)
         if self.fwd_early and W == 1:
             self.side2.wait_stream(self.main)                # the all_df rows
-            with self.ctx.on(self.side2) as h2:
-                self._analyzer_fwd(h2)
+            with self.ctx.on(self.side2):
+                self._analyzer_fwd()
         if one_pass:
             mark("zstats", 0)
             if self.A_r > 0:
                 if lab_side:
                     self.main.wait_event(self.labels_done)          # tmr_ret1d is a feature
-                self._zstats(h, self.nch, self.T)
+                self._zstats(self.nch, self.T)
             mark("zstats", 1)
         if W > 1:           # full-width label planes for the rebalance, during the Grams
             self._labels(self.side2, full=True)
@@ -726,19 +699,18 @@ class Pipeline:
                 # all_df rows only (not the predictions): gathered now, beside the Grams, so
                 # the analyzer's prediction-dependent chain starts right at the predict
                 self.side2.wait_stream(self.main)            # the all_df rows (after zstats)
-                with self.ctx.on(self.side2) as h2:
+                with self.ctx.on(self.side2):
                     self._gather_alldf()
-                    self._analyzer_fwd(h2)
+                    self._analyzer_fwd()
 
-    def _stage_gram(self, h, mark):
+    def _stage_gram(self, mark):
         """xs_gram: the pooled Gram of the train + valid rows (block results, N > 1: exchanged,
         then the block level of the tree), train_end's Gram added once more."""
-        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
-        sp, p, W = self.sp, self.p, self.W
+        call, sp, p, W = self.ctx.call, self.sp, self.p, self.W
         mark("xs_gram", 0)
-        self._pooled_blocks(h, 0, sp.v1, mark=mark)             # train + valid rows
+        self._pooled_blocks(0, sp.v1, mark=mark)                # train + valid rows
         if sp.dup:                                              # train_end counted twice
-            self._te_subtree(h, sp.tr1 - 1)
+            self._te_subtree(sp.tr1 - 1)
         if W > 1:
             mark("exchange", 0)
             gb = self.comm.all_gather(self.pool_blk)            # [W][nblk_r + 1][part]
@@ -748,12 +720,10 @@ class Pipeline:
             blocks, te_leaves, nte = self.pool_all, self.te_all, W
         else:
             blocks, te_leaves, nte = self.pool_blk, self.pool_blk[self.nblk_r:], 1
-        chk(L.afm_gram_tree_f64(h, p, P(blocks), N_BLOCKS, N_BLOCKS, 1, P(self.pool_g)),
-            "tree blocks")
+        call("afm_gram_tree_f64", p, blocks, N_BLOCKS, N_BLOCKS, 1, self.pool_g)
         if sp.dup:
-            chk(L.afm_gram_tree_f64(h, p, P(te_leaves), nte, nte, 1, P(self.te_gram)),
-                "tree train_end")
-            chk(L.afm_vec_add_f64(h, self.p2 * self.p2, P(self.te_gram), P(self.pool_g)), "dup")
+            call("afm_gram_tree_f64", p, te_leaves, nte, nte, 1, self.te_gram)
+            call("afm_vec_add_f64", self.p2 * self.p2, self.te_gram, self.pool_g)
         mark("xs_gram", 1)
 
     def _fork_fm(self, at, mark):
@@ -766,81 +736,76 @@ class Pipeline:
         if at != self.fm_at:
             return
         self.side.wait_stream(self.main)
-        with self.ctx.on(self.side) as hs:
+        with self.ctx.on(self.side):
             mark("fm", 0)
-            self._fm_local(hs)
+            self._fm_local()
             if self.W == 1:
-                self._fm_solve(hs, self.fm_sub)
-                self._fm_stats(hs)
+                self._fm_solve(self.fm_sub)
+                self._fm_stats()
             mark("fm", 1)
 
-    def _stage_fit_predict(self, h, mark):
+    def _stage_fit_predict(self, mark):
         """lasso + predict (N > 1: the test dates' whole cross-section gathered)."""
-        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
-        c, sp, T, lda_r, p = self.cfg, self.sp, self.T, self.lda_r, self.p
+        call, c, sp, T, lda_r, p = self.ctx.call, self.cfg, self.sp, self.T, self.lda_r, self.p
         self._fork_fm("gram", mark)
         mark("lasso", 0)
-        chk(L.afm_lasso_fit_f64(h, P(self.pool_g), P(self.pool_s), p, c.alpha, c.max_iter,
-                                c.lasso_tol, 0, P(self.lasso_beta), P(self.lasso_info)), "lasso")
+        call("afm_lasso_fit_f64", self.pool_g, self.pool_s, p, c.alpha, c.max_iter, c.lasso_tol,
+             0, self.lasso_beta, self.lasso_info)
         mark("lasso", 1)
         mark("predict", 0)
         if self.A_r > 0:
-            chk(L.afm_zpredict_f64(h, P(self.out), T * lda_r, lda_r, sp.s0, T - sp.s0,
-                                   P(self.feat), p, P(self.zs), P(self.lasso_beta),
-                                   P(self.zrows), P(self.pred_r)), "predict")
+            call("afm_zpredict_f64", self.out, T * lda_r, lda_r, sp.s0, T - sp.s0, self.feat, p,
+                 self.zs, self.lasso_beta, self.zrows, self.pred_r)
         if self.W > 1:                          # the whole cross-section of the test dates
             self._gather_test_planes()
         mark("predict", 1)
         self._fork_fm("predict", mark)
 
-    def _stage_tail(self, h, mark):
+    def _stage_tail(self, mark):
         """The analyzer forked onto the second side stream; rebalance and pnl on the main stream;
         N > 1: the scan on its own stream beside the FM exchange and the analyzer's series."""
-        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
         c, sp, full, W = self.cfg, self.sp, self.full, self.W
         if c.analyzer:
             self.side2.wait_stream(self.main)
-            with self.ctx.on(self.side2) as h2:
-                self._analyzer(h2, mark)
+            with self.ctx.on(self.side2):
+                self._analyzer(mark)
         self._fork_fm("analyzer", mark)
         mark("rebalance", 0)
         if W > 1:
             self.main.wait_event(self.labels_done)     # the label planes
         x, ne = self.reb_ext, self.e1 - self.e0
         if ne > 0:
-            chk(L.afm_rebalance_f64(h, self.T, full.A, full.lda, P(self.rd_ext), ne, P(self.pred),
-                                    P(full.tbits), P(self.target), P(self.zrows_full), 0,
-                                    sp.tr1, -1 if c.window is None else int(c.window),
-                                    P(full.close), P(self.tmr), c.top_n, c.lo, c.hi,
-                                    P(x["k"]), P(x["books"]), P(x["weights"]), P(x["sums"]),
-                                    P(x["upos"]), P(x["usize"]), P(x["status"])), "rebalance")
+            self.ctx.call("afm_rebalance_f64", self.T, full.A, full.lda, self.rd_ext, ne,
+                          self.pred, full.tbits, self.target, self.zrows_full, 0, sp.tr1,
+                          -1 if c.window is None else int(c.window), full.close, self.tmr,
+                          c.top_n, c.lo, c.hi, x["k"], x["books"], x["weights"], x["sums"],
+                          x["upos"], x["usize"], x["status"])
         if self.reb_split:
             self._gather_rebalance()
         mark("rebalance", 1)
         self._fork_fm("rebalance", mark)
         if W == 1:
-            self._pnl_scan(h, mark)
+            self._pnl_scan(mark)
             return
         # the scan on its own stream; the FM exchange (per-date subtrees -> date owners, solves,
         # betas) and the analyzer's gather + series run beside it on the main and second side
         # streams, issued in this order on every rank (RCCL runs a group's collectives in issue
         # order)
         self.side3.wait_stream(self.main)
-        with self.ctx.on(self.side3) as h3:
-            self._pnl_scan(h3, mark)
+        with self.ctx.on(self.side3):
+            self._pnl_scan(mark)
         self.main.wait_stream(self.side)
-        self._fm_exchange(h)
+        self._fm_exchange()
         if c.analyzer:
-            with self.ctx.on(self.side2) as h2:
-                self._analyzer_series(h2, mark)
+            with self.ctx.on(self.side2):
+                self._analyzer_series(mark)
 
-    def _pnl_scan(self, h, mark):
-        L, P, c, r, q = _lib.lib(), _lib.ptr, self.cfg, self.reb, self.pnl
+    def _pnl_scan(self, mark):
+        c, r, q = self.cfg, self.reb, self.pnl
         mark("pnl", 0)
-        _lib.check(L.afm_pnl_scan_f64(h, self.nd, P(r["k"]), P(r["books"]), P(r["sums"]),
-                                      P(r["upos"]), P(r["usize"]), c.v0, c.rate, P(q["value"]),
-                                      P(q["turnover"]), P(q["long_ret"]), P(q["short_ret"])),
-                   "pnl")
+        self.ctx.call("afm_pnl_scan_f64", self.nd, r["k"], r["books"], r["sums"], r["upos"],
+                      r["usize"], c.v0, c.rate, q["value"], q["turnover"], q["long_ret"],
+                      q["short_ret"])
         mark("pnl", 1)
 
     # ---- exchanges (N > 1; a collective runs on the current stream and leaves the binding) ----
@@ -940,73 +905,65 @@ class Pipeline:
             sb.parts[0][:, :self.A_r].copy_(self.alldf[:, :self.A_r])
         self._place(self.alldf_full, self.comm.all_gather_buffer(sb)[0])
 
-    def _fm_exchange(self, h):
+    def _fm_exchange(self):
         """The per-date subtrees to the date owners (one all_to_all), their solves, then every
         rank gets every date's betas (one packed all-gather) and the FM statistics."""
         W = self.W
         recv = self.comm.all_to_all(self.fm_sub, [b - a for a, b in self.fdr],
                                     [self.fnd] * W)                          # [W * fnd][part]
         sub = recv.view(W, self.fnd, self.pef).transpose(0, 1).contiguous()   # [fnd][W][part]
-        self._fm_solve(h, sub)
+        self._fm_solve(sub)
         got = self.comm.all_gather_packed([self.fm_beta_own, self.fm_nobs_own, self.fm_rank_own])
         self._place_shares("fm", self.fdr, got, (self.fm_beta, self.fm_nobs, self.fm_rank))
-        self._fm_stats(h)
+        self._fm_stats()
 
     # ---- the analyzer (second side stream) ------------------------------------------------------
-    def _analyzer(self, h, mark):
+    def _analyzer(self, mark):
         """AlphaSignalAnalyzer(lasso_predict, price_data=df_test[['close_price']]).run()
         (KKT:630-631) on the test sub-grid, no host synchronisation."""
-        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
-        full, sp, an = self.full, self.sp, self.an
+        call, full, sp, an = self.ctx.call, self.full, self.sp, self.an
         lda, a0, Ta = full.lda, self.an_a0, self.Ta
         mark("analyzer", 0)
         if not self.fwd_early:
-            self._analyzer_fwd(h)
+            self._analyzer_fwd()
         j0, j1 = self.an_rng
         d0 = sp.s0 - a0 + j0                        # sub-grid dates [d0, d1) of this rank
         d1 = d0 + (j1 - j0)
         if j1 > j0:
-            chk(L.afm_xs_prepare_range_f64(h, Ta, full.A, lda, d0, d1, P(self.pred[a0:]),
-                                           P(an["fr"]), P(an["scratch"]), P(an["rows"]),
-                                           P(an["rows_idx"]), P(an["nrows"])), "xs_prepare")
-            chk(L.afm_xs_layers_f64(h, d1 - d0, lda, P(an["rows"][0, d0:]), P(an["nrows"][d0:]),
-                                    P(an["skey"][d0:]), P(an["sidx"][d0:]), P(an["ra"][d0:]),
-                                    P(an["rd"][d0:])), "xs_layers")
-            chk(L.afm_xs_stats_f64(h, Ta, lda, P(self.an_dates[j0:]), j1 - j0, P(an["rows"]),
-                                   P(an["nrows"]), P(an["ra"]), P(an["rd"]), 10, P(an["ic"][j0:]),
-                                   P(an["layer_mean"][j0:]), P(an["layer_cnt"][j0:]),
-                                   P(an["port"][j0:])), "xs_stats")
+            call("afm_xs_prepare_range_f64", Ta, full.A, lda, d0, d1, self.pred[a0:], an["fr"],
+                 an["scratch"], an["rows"], an["rows_idx"], an["nrows"])
+            call("afm_xs_layers_f64", d1 - d0, lda, an["rows"][0, d0:], an["nrows"][d0:],
+                 an["skey"][d0:], an["sidx"][d0:], an["ra"][d0:], an["rd"][d0:])
+            call("afm_xs_stats_f64", Ta, lda, self.an_dates[j0:], j1 - j0, an["rows"],
+                 an["nrows"], an["ra"], an["rd"], 10, an["ic"][j0:], an["layer_mean"][j0:],
+                 an["layer_cnt"][j0:], an["port"][j0:])
         if self.W > 1:
             return          # the all-gather and the series follow the main chain's exchanges
-        self._analyzer_series(h, mark)
+        self._analyzer_series(mark)
 
-    def _analyzer_fwd(self, h):
+    def _analyzer_fwd(self):
         """The analyzer's df_test price rows and forward returns (KKT:294-296): they read the close
         plane and the all_df rows only, not the predictions."""
-        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
-        full, sp, an, a0 = self.full, self.sp, self.an, self.an_a0
-        chk(L.afm_row_bits(h, self.nch, full.lda, P(self.alldf_full), None, None, sp.s0, self.T,
-                           P(self.price_bits)), "price rows")
-        chk(L.afm_fwd_returns_f64(h, self.Ta, full.lda, P(full.close[a0:]),
-                                  P(self.price_bits[a0 // 64:]), P(an["fr"])), "fwd_returns")
+        call, full, sp, a0 = self.ctx.call, self.full, self.sp, self.an_a0
+        call("afm_row_bits", self.nch, full.lda, self.alldf_full, None, None, sp.s0, self.T,
+             self.price_bits)
+        call("afm_fwd_returns_f64", self.Ta, full.lda, full.close[a0:],
+             self.price_bits[a0 // 64:], self.an["fr"])
 
-    def _analyzer_series(self, h, mark):
-        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
+    def _analyzer_series(self, mark):
         an = self.an
         if self.W > 1:
             self._gather_analyzer()
-        chk(L.afm_xs_series_f64(h, self.an_nd, P(an["layer_mean"]), P(an["port"]), P(an["ic"]),
-                                P(self.an_year), self.an_nyears, self.an_year0,
-                                P(an["cum_layer"]), P(an["ls"]), P(an["cum_port"]), P(an["ir"]),
-                                P(an["ir_scratch"])), "xs_series")
+        self.ctx.call("afm_xs_series_f64", self.an_nd, an["layer_mean"], an["port"], an["ic"],
+                      self.an_year, self.an_nyears, self.an_year0, an["cum_layer"], an["ls"],
+                      an["cum_port"], an["ir"], an["ir_scratch"])
         mark("analyzer", 1)
 
-    def _range_gram(self, h, t0, nt, bufs, gram):
+    def _range_gram(self, t0, nt, bufs, gram):
         """The pooled Gram of the z-score rows of the dates [t0, t0 + nt) -> gram [1][p+2][p+2]:
         ``_pooled_blocks`` in the buffers ``bufs`` (not the step's) + the block level."""
-        self._pooled_blocks(h, t0, nt, bufs)
-        _lib.check(_lib.lib().afm_gram_tree_f64(h, self.p, _lib.ptr(bufs[3]), N_BLOCKS, N_BLOCKS,
-                                                1, _lib.ptr(gram)), "tree blocks")
+        self._pooled_blocks(t0, nt, bufs)
+        self.ctx.call("afm_gram_tree_f64", self.p, bufs[3], N_BLOCKS, N_BLOCKS, 1, gram)
 
     def lasso_cv(self, alphas=None, *, n_alphas: int = 100, eps: float = 1e-3) -> dict:
         """Validation-scored alpha selection on the last ``step()``'s panel (one GPU): the
@@ -1028,7 +985,6 @@ class Pipeline:
             raise NotImplementedError("lasso_cv() runs on one GPU (world = 1)")
         if self.nrb == 0:
             raise ValueError("lasso_cv(): the panel has no assets")
-        L, P, chk = _lib.lib(), _lib.ptr, _lib.check
         c, sp, p = self.cfg, self.sp, self.p
         if getattr(self, "_cv_bufs", None) is None:
             self._cv_bufs = tuple(torch.empty_like(b) for b in (self.pool_part, self.pool_c1,
@@ -1036,9 +992,9 @@ class Pipeline:
             self._cv_gram = torch.empty((2, self.p2, self.p2), dtype=torch.float64,
                                         device=self.out.device)
         gram, shift = self._cv_gram, self.pool_s.expand(2, self.p2).contiguous()
-        with self.ctx.on(torch.cuda.current_stream(self.out.device)) as h:   # the caller's stream
-            self._range_gram(h, 0, sp.tr1, self._cv_bufs, gram[0:1])
-            self._range_gram(h, sp.v0, sp.v1 - sp.v0, self._cv_bufs, gram[1:2])
+        with self.ctx.on(torch.cuda.current_stream(self.out.device)):        # the caller's stream
+            self._range_gram(0, sp.tr1, self._cv_bufs, gram[0:1])
+            self._range_gram(sp.v0, sp.v1 - sp.v0, self._cv_bufs, gram[1:2])
             a = _given_alphas(alphas) if alphas is not None else \
                 alpha_grid(gram[0].cpu().numpy(), p, eps, n_alphas)
             beta, info = lasso_batch(gram[0:1], shift[0:1], p, torch.from_numpy(a).to(gram.device),
@@ -1048,9 +1004,8 @@ class Pipeline:
             best = int(np.argmin(score[:, 1]))
             refit = torch.empty(p + 1, dtype=torch.float64, device=gram.device)
             rinfo = torch.empty(3, dtype=torch.float64, device=gram.device)
-            chk(L.afm_lasso_fit_f64(h, P(self.pool_g), P(self.pool_s), p, float(a[best]),
-                                    c.max_iter, c.lasso_tol, 0, P(refit), P(rinfo)),
-                "lasso refit")
+            self.ctx.call("afm_lasso_fit_f64", self.pool_g, self.pool_s, p, float(a[best]),
+                          c.max_iter, c.lasso_tol, 0, refit, rinfo)
         info_h = info[0].cpu().numpy()
         return {"alphas": a, "coefs": beta[0].cpu().numpy(),
                 "n_iter": info_h[:, 2].astype(np.int64), "dual_gap": info_h[:, 0] / n_train,

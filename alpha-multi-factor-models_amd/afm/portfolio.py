@@ -49,13 +49,10 @@ def rebalance(pred, trad_bits, hist, hist_bits, close, tmr, dates_idx, *, A: int
         "status": torch.empty(nd, dtype=torch.int32, device=dev),
     }
     h0, h1 = h_range if h_range is not None else (0, T)
-    ctx = _lib.Context.get(dev.index)
-    P = _lib.ptr
-    _lib.check(_lib.lib().afm_rebalance_f64(
-        ctx.bind_stream(), T, A, lda, P(dates_idx), nd, P(pred), P(trad_bits), P(hist),
-        P(hist_bits), h0, h1, -1 if window is None else int(window), P(close), P(tmr), int(top_n),
-        float(lo), float(hi), P(out["k"]), P(out["books"]), P(out["weights"]), P(out["sums"]),
-        P(out["upos"]), P(out["usize"]), P(out["status"])), "afm_rebalance_f64")
+    _lib.run("afm_rebalance_f64", T, A, lda, dates_idx, nd, pred, trad_bits, hist, hist_bits, h0,
+             h1, -1 if window is None else int(window), close, tmr, int(top_n), float(lo),
+             float(hi), out["k"], out["books"], out["weights"], out["sums"], out["upos"],
+             out["usize"], out["status"])
     return out
 
 
@@ -68,12 +65,9 @@ def pnl_scan(reb: dict, v0: float = V0, rate: float = 1e-4):
            "turnover": torch.empty(nd, dtype=torch.float64, device=dev),
            "long_ret": torch.empty(nd, dtype=torch.float64, device=dev),
            "short_ret": torch.empty(nd, dtype=torch.float64, device=dev)}
-    ctx = _lib.Context.get(dev.index)
-    P = _lib.ptr
-    _lib.check(_lib.lib().afm_pnl_scan_f64(
-        ctx.bind_stream(), nd, P(reb["k"]), P(reb["books"]), P(reb["sums"]), P(reb["upos"]),
-        P(reb["usize"]), float(v0), float(rate), P(res["value"]), P(res["turnover"]),
-        P(res["long_ret"]), P(res["short_ret"])), "afm_pnl_scan_f64")
+    _lib.run("afm_pnl_scan_f64", nd, reb["k"], reb["books"], reb["sums"], reb["upos"],
+             reb["usize"], float(v0), float(rate), res["value"], res["turnover"], res["long_ret"],
+             res["short_ret"])
     return res
 
 
@@ -98,13 +92,9 @@ def bootstrap_pnl(reb: dict, pred, dates_idx, paths, v0: float = V0, rate: float
            "turnover": torch.empty((npaths, steps), dtype=torch.float64, device=dev),
            "long_ret": torch.empty((npaths, steps), dtype=torch.float64, device=dev),
            "short_ret": torch.empty((npaths, steps), dtype=torch.float64, device=dev)}
-    ctx = _lib.Context.get(dev.index)
-    P = _lib.ptr
-    _lib.check(_lib.lib().afm_bootstrap_pnl_f64(
-        ctx.bind_stream(), int(pred.shape[1]), P(dates_idx), nd, P(pred), P(reb["k"]),
-        P(reb["books"]), P(reb["sums"]), npaths, steps, P(paths), float(v0), float(rate),
-        P(res["value"]), P(res["turnover"]), P(res["long_ret"]), P(res["short_ret"])),
-        "afm_bootstrap_pnl_f64")
+    _lib.run("afm_bootstrap_pnl_f64", int(pred.shape[1]), dates_idx, nd, pred, reb["k"],
+             reb["books"], reb["sums"], npaths, steps, paths, float(v0), float(rate), res["value"],
+             res["turnover"], res["long_ret"], res["short_ret"])
     return res
 
 
@@ -121,11 +111,7 @@ def min_variance_weights(returns, lo: float = 0.0, hi: float = 0.1):
     w = torch.empty(k, dtype=torch.float64, device=R.device)
     cov = torch.empty((k, k), dtype=torch.float64, device=R.device)
     st = torch.empty(1, dtype=torch.int32, device=R.device)
-    ctx = _lib.Context.get(R.device.index)
-    P = _lib.ptr
-    _lib.check(_lib.lib().afm_min_variance_weights_f64(ctx.bind_stream(), P(R), rows, k, k,
-                                                       float(lo), float(hi), P(w), P(cov),
-                                                       P(st)), "afm_min_variance_weights_f64")
+    _lib.run("afm_min_variance_weights_f64", R, rows, k, k, float(lo), float(hi), w, cov, st)
     return w.cpu().numpy(), cov.cpu().numpy()
 
 

@@ -34,12 +34,8 @@ def xs_gram(base, col_stride: int, seg_stride: int, seg_rows: int, cols, ycol: i
     p = int(cols_t.numel())
     gram = torch.empty((nseg, p + 2, p + 2), dtype=torch.float64, device=dev)
     shift = torch.empty((nseg, p + 2), dtype=torch.float64, device=dev)
-    ctx = _lib.Context.get(dev.index)
-    P = _lib.ptr
-    _lib.check(_lib.lib().afm_xs_gram_f64(
-        ctx.bind_stream(), P(base), col_stride, seg_stride, seg_rows, row_limit, P(cols_t), p,
-        int(ycol), P(bits) if bits is not None else None, seg0, nseg, P(gram), P(shift)),
-        "afm_xs_gram_f64")
+    _lib.run("afm_xs_gram_f64", base, col_stride, seg_stride, seg_rows, row_limit, cols_t, p,
+             int(ycol), bits, seg0, nseg, gram, shift)
     return gram, shift
 
 
@@ -51,10 +47,7 @@ def ols_solve(gram, shift, p: int, tol: float = DEFAULT_TOL):
     beta = torch.empty((nseg, p + 1), dtype=torch.float64, device=dev)
     nobs = torch.empty(nseg, dtype=torch.float64, device=dev)
     rank = torch.empty(nseg, dtype=torch.int32, device=dev)
-    ctx = _lib.Context.get(dev.index)
-    P = _lib.ptr
-    _lib.check(_lib.lib().afm_ols_solve_f64(ctx.bind_stream(), P(gram), P(shift), p, nseg, tol,
-                                            P(beta), P(nobs), P(rank)), "afm_ols_solve_f64")
+    _lib.run("afm_ols_solve_f64", gram, shift, p, nseg, tol, beta, nobs, rank)
     return beta, nobs, rank
 
 
@@ -64,11 +57,8 @@ def pool_moments(gram, shift, p: int):
     dev = gram.device
     g = torch.empty((1, p + 2, p + 2), dtype=torch.float64, device=dev)
     s = torch.empty((1, p + 2), dtype=torch.float64, device=dev)
-    ctx = _lib.Context.get(dev.index)
-    P = _lib.ptr
-    _lib.check(_lib.lib().afm_pool_moments_f64(ctx.bind_stream(), P(gram.contiguous()),
-                                               P(shift.contiguous()), p, gram.shape[0], P(g),
-                                               P(s)), "afm_pool_moments_f64")
+    _lib.run("afm_pool_moments_f64", gram.contiguous(), shift.contiguous(), p, gram.shape[0], g,
+             s)
     return g, s
 
 
@@ -78,11 +68,7 @@ def fama_macbeth(beta, rank):
     k = beta.shape[1]
     m = torch.empty(k, dtype=torch.float64, device=beta.device)
     t = torch.empty(k, dtype=torch.float64, device=beta.device)
-    ctx = _lib.Context.get(beta.device.index)
-    P = _lib.ptr
-    _lib.check(_lib.lib().afm_fama_macbeth_f64(ctx.bind_stream(), P(beta), P(rank),
-                                               beta.shape[0], k, P(m), P(t)),
-               "afm_fama_macbeth_f64")
+    _lib.run("afm_fama_macbeth_f64", beta, rank, beta.shape[0], k, m, t)
     return m, t
 
 
@@ -95,13 +81,9 @@ def predict_grid(planes, lda: int, cols, beta, bits, t0: int, nt: int, per_date:
     cols_t = torch.as_tensor(np.asarray(cols, dtype=np.int32), device=dev)
     if out is None:
         out = torch.full((T, lda), float("nan"), dtype=torch.float64, device=dev)
-    ctx = _lib.Context.get(dev.index)
-    P = _lib.ptr
     stride = beta.shape[-1] if per_date else 0
-    _lib.check(_lib.lib().afm_predict_f64(ctx.bind_stream(), P(planes), T * lda, lda, t0, nt,
-                                          P(cols_t), int(cols_t.numel()), P(beta.contiguous()),
-                                          stride, P(bits), int(ycheck), P(out)),
-               "afm_predict_f64")
+    _lib.run("afm_predict_f64", planes, T * lda, lda, t0, nt, cols_t, int(cols_t.numel()),
+             beta.contiguous(), stride, bits, int(ycheck), out)
     return out
 
 
@@ -152,17 +134,9 @@ class LinearRegression:
 
     def fit(self, X, y):
         import torch
-        Xc, n, p, names = self._as_columns(X)
-        yv = y.to_numpy(dtype=np.float64) if hasattr(y, "to_numpy") else y
-        y2d = (getattr(yv, "ndim", 1) == 2)
-        yt = torch.as_tensor(np.asarray(yv, dtype=np.float64) if not isinstance(yv, torch.Tensor)
-                             else yv, dtype=torch.float64).to(_dev()).reshape(-1)
-        if yt.numel() != n:
-            raise ValueError(f"X has {n} rows, y has {yt.numel()}")
-        if not (torch.isfinite(Xc).all() and torch.isfinite(yt).all()):
-            raise ValueError("Input contains NaN or infinity (as scikit-learn rejects it)")
+        Z, n, p, names, y2d = _design(X, y)
         # Z = [x_1..x_p, y, r]: the residual column r drives the refinement passes
-        Z = torch.cat([Xc, yt.view(1, -1), torch.zeros_like(yt).view(1, -1)], dim=0).contiguous()
+        Z = torch.cat([Z, torch.zeros_like(Z[:1])], dim=0)
         nseg = (n + SEG_ROWS - 1) // SEG_ROWS
         gram, shift = xs_gram(Z, n, SEG_ROWS, SEG_ROWS, list(range(p)), p, nseg=nseg,
                               row_limit=n)
@@ -170,19 +144,15 @@ class LinearRegression:
         beta, nobs, rank = ols_solve(g, s, p, self.tol)
         # semi-normal equations + iterative refinement (accuracy ~ cond(X) eps instead of
         # cond(X)^2 eps, as scikit-learn's SVD-based lstsq): beta += C^-1 Xc' r
-        L, P = _lib.lib(), _lib.ptr
-        h = _lib.Context.get(Z.device.index).bind_stream()
         mean = s[0].contiguous()
         for _ in range(self.refine):
-            _lib.check(L.afm_ols_residual_f64(h, P(Z), n, p, p, P(mean), P(beta[0]), P(Z[p + 1])),
-                       "ols_residual")
+            _lib.run("afm_ols_residual_f64", Z, n, p, p, mean, beta[0], Z[p + 1])
             gr, sr = xs_gram(Z, n, SEG_ROWS, SEG_ROWS, list(range(p)), p + 1, nseg=nseg,
                              row_limit=n)
             g2, s2 = pool_moments(gr, sr, p)
             delta, _, _ = ols_solve(g2, s2, p, self.tol)
-            _lib.check(L.afm_vec_add_f64(h, p, P(delta[0, 1:].contiguous()),
-                                         P(beta[0, 1:])), "vec_add")
-        _lib.check(L.afm_ols_intercept_f64(h, p, P(mean), P(beta[0])), "ols_intercept")
+            _lib.run("afm_vec_add_f64", p, delta[0, 1:].contiguous(), beta[0, 1:])
+        _lib.run("afm_ols_intercept_f64", p, mean, beta[0])
         b = beta[0].cpu().numpy()
         self.rank_ = int(rank[0].item())
         self.n_features_in_ = p
@@ -199,18 +169,23 @@ class LinearRegression:
         return self
 
     def predict(self, X):
-        import torch
-        Xc, n, p, _ = self._as_columns(X)
-        if p != self.n_features_in_:
-            raise ValueError(f"X has {p} features, model was fit with {self.n_features_in_}")
-        lda = (n + 63) // 64 * 64
-        base = torch.zeros((p, lda), dtype=torch.float64, device=Xc.device)
-        base[:, :n] = Xc
-        bits = torch.zeros((1, lda), dtype=torch.int64, device=Xc.device)
-        bits[0, :n] = 1
-        out = predict_grid(base.view(p, 1, lda), lda, list(range(p)), self._beta, bits, 0, 1)
-        pred = out[0, :n].cpu().numpy()
+        pred = _predict(self, X)
         return pred.reshape(-1, 1) if self._y2d else pred
+
+
+def _predict(model, X):
+    """The fitted ``model._beta`` (intercept first) applied to the rows of X -> host [n]."""
+    import torch
+    Xc, n, p, _ = LinearRegression._as_columns(X)
+    if p != model.n_features_in_:
+        raise ValueError(f"X has {p} features, model was fit with {model.n_features_in_}")
+    lda = (n + 63) // 64 * 64
+    base = torch.zeros((p, lda), dtype=torch.float64, device=Xc.device)
+    base[:, :n] = Xc
+    bits = torch.zeros((1, lda), dtype=torch.int64, device=Xc.device)
+    bits[0, :n] = 1
+    out = predict_grid(base.view(p, 1, lda), lda, list(range(p)), model._beta, bits, 0, 1)
+    return out[0, :n].cpu().numpy()
 
 
 class ConvergenceWarning(UserWarning):
@@ -256,29 +231,15 @@ class Lasso:
         import warnings
 
         import torch
-        Xc, n, p, names = LinearRegression._as_columns(X)
-        yv = y.to_numpy(dtype=np.float64) if hasattr(y, "to_numpy") else y
-        y2d = getattr(yv, "ndim", 1) == 2
-        yt = torch.as_tensor(np.asarray(yv, dtype=np.float64) if not isinstance(yv, torch.Tensor)
-                             else yv, dtype=torch.float64).to(_dev()).reshape(-1)
-        if yt.numel() != n:
-            raise ValueError(f"X has {n} rows, y has {yt.numel()}")
-        if not (torch.isfinite(Xc).all() and torch.isfinite(yt).all()):
-            raise ValueError("Input contains NaN or infinity (as scikit-learn rejects it)")
+        Z, n, p, names, y2d = _design(X, y)
         if self.alpha == 0:
             warnings.warn("With alpha=0 this is ordinary least squares by coordinate descent; "
                           "LinearRegression is the better tool.", UserWarning)
-        Z = torch.cat([Xc, yt.view(1, -1)], dim=0).contiguous()
-        nseg = (n + SEG_ROWS - 1) // SEG_ROWS
-        gram, shift = xs_gram(Z, n, SEG_ROWS, SEG_ROWS, list(range(p)), p, nseg=nseg,
-                              row_limit=n)
-        g, s = pool_moments(gram, shift, p)
+        g, s = _pooled(Z, p)
         w = torch.empty(p, dtype=torch.float64, device=Z.device)
         info = torch.empty(3, dtype=torch.float64, device=Z.device)
-        h = _lib.Context.get(Z.device.index).bind_stream()
-        _lib.check(_lib.lib().afm_lasso_cd_f64(h, _lib.ptr(g), p, self.alpha * n, 0.0,
-                                               self.max_iter, self.tol, int(self.positive),
-                                               _lib.ptr(w), _lib.ptr(info)), "afm_lasso_cd_f64")
+        _lib.run("afm_lasso_cd_f64", g, p, self.alpha * n, 0.0, self.max_iter, self.tol,
+                 int(self.positive), w, info)
         G = g[0].cpu().numpy()
         mean = s[0].cpu().numpy()[1:] + G[0, 1:] / G[0, 0]
         gap, tol_y, n_iter = info.cpu().numpy()
@@ -298,18 +259,7 @@ class Lasso:
         self._beta = torch.from_numpy(b).to(Z.device)
         return self
 
-    def predict(self, X):
-        import torch
-        Xc, n, p, _ = LinearRegression._as_columns(X)
-        if p != self.n_features_in_:
-            raise ValueError(f"X has {p} features, model was fit with {self.n_features_in_}")
-        lda = (n + 63) // 64 * 64
-        base = torch.zeros((p, lda), dtype=torch.float64, device=Xc.device)
-        base[:, :n] = Xc
-        bits = torch.zeros((1, lda), dtype=torch.int64, device=Xc.device)
-        bits[0, :n] = 1
-        out = predict_grid(base.view(p, 1, lda), lda, list(range(p)), self._beta, bits, 0, 1)
-        return out[0, :n].cpu().numpy()
+    predict = _predict
 
 
 # ---- regularisation paths and validation-scored alpha selection ---------------------------------
@@ -326,13 +276,9 @@ def lasso_batch(gram, shift, p: int, alphas, *, nprob: int = 1, warm: bool = Tru
     nalpha = int(alphas.numel())
     beta = torch.empty((nprob, nalpha, p + 1), dtype=torch.float64, device=dev)
     info = torch.empty((nprob, nalpha, 3), dtype=torch.float64, device=dev)
-    P = _lib.ptr
-    h = _lib.Context.get(dev.index).bind_stream()
     gs, ss = (0, 0) if shared else ((p + 2) * (p + 2), p + 2)
-    _lib.check(_lib.lib().afm_lasso_batch_f64(h, P(gram), gs, P(shift), ss, p, P(alphas), nalpha,
-                                              nprob, int(bool(warm)), int(max_iter), float(tol),
-                                              int(bool(positive)), P(beta), P(info)),
-               "afm_lasso_batch_f64")
+    _lib.run("afm_lasso_batch_f64", gram, gs, shift, ss, p, alphas, nalpha, nprob,
+             int(bool(warm)), int(max_iter), float(tol), int(bool(positive)), beta, info)
     return beta, info
 
 
@@ -343,11 +289,8 @@ def gram_score(gram, shift, p: int, beta, *, shared: bool = False):
     import torch
     nprob, nmodel = int(beta.shape[0]), int(beta.shape[1])
     out = torch.empty((nprob, nmodel, 4), dtype=torch.float64, device=gram.device)
-    P = _lib.ptr
-    h = _lib.Context.get(gram.device.index).bind_stream()
     gs, ss = (0, 0) if shared else ((p + 2) * (p + 2), p + 2)
-    _lib.check(_lib.lib().afm_gram_score_f64(h, P(gram), gs, P(shift), ss, p, P(beta), nmodel,
-                                             nprob, P(out)), "afm_gram_score_f64")
+    _lib.run("afm_gram_score_f64", gram, gs, shift, ss, p, beta, nmodel, nprob, out)
     return out
 
 
@@ -371,20 +314,22 @@ def _given_alphas(alphas) -> np.ndarray:
     return a
 
 
-def _design(X, y):
-    """-> (Z device [p+1][n] = [x_1..x_p, y], n, p, feature names or None)."""
+def _design(X, y, max_features: int | None = None):
+    """-> (Z device [p+1][n] = [x_1..x_p, y], n, p, feature names or None, y was 2-D);
+    ``max_features``: the Lasso path kernels' limit."""
     import torch
     Xc, n, p, names = LinearRegression._as_columns(X)
     yv = y.to_numpy(dtype=np.float64) if hasattr(y, "to_numpy") else y
+    y2d = getattr(yv, "ndim", 1) == 2
     yt = torch.as_tensor(np.asarray(yv, dtype=np.float64) if not isinstance(yv, torch.Tensor)
                          else yv, dtype=torch.float64).to(_dev()).reshape(-1)
     if yt.numel() != n:
         raise ValueError(f"X has {n} rows, y has {yt.numel()}")
     if not (torch.isfinite(Xc).all() and torch.isfinite(yt).all()):
         raise ValueError("Input contains NaN or infinity (as scikit-learn rejects it)")
-    if p > 110:
-        raise ValueError(f"{p} features: the Lasso kernels hold at most 110")
-    return torch.cat([Xc, yt.view(1, -1)], dim=0).contiguous(), n, p, names
+    if max_features is not None and p > max_features:
+        raise ValueError(f"{p} features: the Lasso kernels hold at most {max_features}")
+    return torch.cat([Xc, yt.view(1, -1)], dim=0).contiguous(), n, p, names, y2d
 
 
 def _pooled(Z, p: int):
@@ -405,7 +350,7 @@ def lasso_path(X, y, *, eps: float = 1e-3, n_alphas: int = 100, alphas=None, tol
     import torch
     if tol < 0 or max_iter < 1:
         raise ValueError("tol must be >= 0 and max_iter >= 1")
-    Z, n, p, _ = _design(X, y)
+    Z, n, p, _, _ = _design(X, y, 110)
     g, s = _pooled(Z, p)
     a = _given_alphas(alphas) if alphas is not None else alpha_grid(g[0].cpu().numpy(), p, eps,
                                                                     n_alphas)
@@ -457,7 +402,7 @@ class LassoCV:
         import warnings
 
         import torch
-        Z, n, p, names = _design(X, y)
+        Z, n, p, names, _ = _design(X, y, 110)
         dev = Z.device
         g, s = _pooled(Z, p)
         a = self.alphas if self.alphas is not None else alpha_grid(g[0].cpu().numpy(), p,
@@ -487,10 +432,8 @@ class LassoCV:
         self.alpha_ = float(a[best])
         b = torch.empty(p + 1, dtype=torch.float64, device=dev)
         info = torch.empty(3, dtype=torch.float64, device=dev)
-        h = _lib.Context.get(dev.index).bind_stream()
-        _lib.check(_lib.lib().afm_lasso_fit_f64(h, _lib.ptr(g), _lib.ptr(s), p, self.alpha_,
-                                                self.max_iter, self.tol, int(self.positive),
-                                                _lib.ptr(b), _lib.ptr(info)), "afm_lasso_fit_f64")
+        _lib.run("afm_lasso_fit_f64", g, s, p, self.alpha_, self.max_iter, self.tol,
+                 int(self.positive), b, info)
         bh = b.cpu().numpy()
         gap, tol_y, n_iter = info.cpu().numpy()
         self.coef_, self.intercept_ = bh[1:].copy(), float(bh[0])
@@ -504,4 +447,4 @@ class LassoCV:
         self._beta = b
         return self
 
-    predict = Lasso.predict
+    predict = _predict

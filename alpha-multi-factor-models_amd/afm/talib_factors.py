@@ -44,11 +44,7 @@ def talib_panel(grid: PanelGrid, out=None):
         out = torch.full((TALIB_COLS, T, lda), float("nan"), dtype=torch.float64,
                          device=grid.device)
     assert out.shape == (TALIB_COLS, T, lda) and out.dtype == torch.float64
-    ctx = _lib.Context.get(grid.device.index)
-    P = _lib.ptr
-    _lib.check(_lib.lib().afm_talib_factors_f64(ctx.bind_stream(), T, grid.A, lda, P(grid.close),
-                                                P(grid.volume), P(grid.vbits), P(out)),
-               "afm_talib_factors_f64")
+    _lib.run("afm_talib_factors_f64", T, grid.A, lda, grid.close, grid.volume, grid.vbits, out)
     return out
 
 

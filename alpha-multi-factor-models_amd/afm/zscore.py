@@ -48,14 +48,10 @@ def zscore_grid(planes, lda: int, cols, bits, train, apply=None, out=None, out_c
     mu = torch.empty((K, lda), dtype=torch.float64, device=dev)
     sd = torch.empty((K, lda), dtype=torch.float64, device=dev)
     keep = torch.zeros_like(bits)
-    ctx = _lib.Context.get(dev.index)
-    P, L = _lib.ptr, _lib.lib()
-    _lib.check(L.afm_zscore_stats_f64(ctx.bind_stream(), P(planes), cs, T, lda, P(cols_t), K,
-                                      P(bits), int(train[0]), int(train[1]), P(mu), P(sd)),
-               "afm_zscore_stats_f64")
-    _lib.check(L.afm_zscore_apply_f64(ctx.bind_stream(), P(planes), cs, T, lda, P(cols_t), K,
-                                      P(bits), int(a0), int(a1), P(mu), P(sd), P(out), ocs,
-                                      P(ocols_t), P(keep)), "afm_zscore_apply_f64")
+    _lib.run("afm_zscore_stats_f64", planes, cs, T, lda, cols_t, K, bits, int(train[0]),
+             int(train[1]), mu, sd)
+    _lib.run("afm_zscore_apply_f64", planes, cs, T, lda, cols_t, K, bits, int(a0), int(a1), mu, sd,
+             out, ocs, ocols_t, keep)
     return mu, sd, keep
 
 

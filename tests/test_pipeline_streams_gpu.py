@@ -122,3 +122,25 @@ def test_marks_recorded(grid, place, emu, path):
     if path == "one_pass":
         k_factor = ev["k_factor"][0].elapsed_time(ev["k_factor"][1])
         assert 0 < k_factor <= ms["factors"]
+
+
+def test_call_refuses_wrong_buffers_before_the_library(monkeypatch):
+    """Context.call checks a buffer against the parameter's declared element type: an int64 tensor
+    or a strided view where afm_vec_add_f64 takes double* is refused in Python -- the library is
+    not entered -- and the well-formed call adds the vectors."""
+    import torch
+    from afm import _lib
+    torch.cuda.set_device(0)
+    proxy = BoundLib(_lib.lib(), _lib.Context.get(0))
+    monkeypatch.setattr(_lib, "lib", lambda: proxy)
+    x = torch.arange(64, dtype=torch.float64, device="cuda")
+    y = torch.ones(64, dtype=torch.float64, device="cuda")
+    wide = torch.zeros(128, dtype=torch.float64, device="cuda")
+    with pytest.raises(_lib.AfmError, match="afm_vec_add_f64 argument 2"):
+        _lib.run("afm_vec_add_f64", 64, x.long(), y)
+    with pytest.raises(_lib.AfmError, match="afm_vec_add_f64 argument 2"):
+        _lib.run("afm_vec_add_f64", 64, wide[::2], y)
+    assert proxy.launches == 0
+    _lib.run("afm_vec_add_f64", 64, x, y)
+    torch.cuda.synchronize()
+    assert proxy.launches == 1 and torch.equal(y, x + 1)

@@ -58,9 +58,9 @@ def main():
                                    P(pipe.zs), pipe.p, P(pipe.zrows), 0, v1, 0, pipe.nrb, pipe.A,
                                    64, P(pipe.pool_part), a.grid), "zpool")
         ev[1].record()
-        pipe._pooled_blocks(h, 0, v1)
+        pipe._pooled_blocks(0, v1)
         ev[2].record()
-        pipe._fm_local(h)
+        pipe._fm_local()
         ev[3].record()
         torch.cuda.synchronize()
         tz.append(ev[0].elapsed_time(ev[1]))
