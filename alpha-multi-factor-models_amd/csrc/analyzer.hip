@@ -941,8 +941,9 @@ __device__ double seq_np_sum(const double* a, int64_t n) {      // np.add.reduce
 
 // One workgroup.  Every series is a sequential recurrence over the dates, so each runs in one
 // lane; its inputs are read in batches of kSerB (all issued before the batch's dependent sums and
-// stores), and the per-year IC samples of the IR sit in LDS when they fit (at most 366 dates a
-// year): a lane that waited for each date's load in turn took ~0.5 ms for ~1,000 dates.
+// stores), and the per-year IC samples of the IR sit in LDS (up to 366 of a year; a year with
+// more dates uses the lane's scratch row instead): a lane that waited for each date's load in
+// turn took ~0.5 ms for ~1,000 dates.
 constexpr int kSerB = 16;
 constexpr int kSerYearCap = 366;
 
@@ -1011,7 +1012,11 @@ __global__ __launch_bounds__(1024) void xs_series_kernel(int64_t nd, const doubl
     if (tid >= 64 && tid < 64 + 3 * nyears) {              // IR per (year, type)
         const int q = tid - 64;
         const int y = q / 3, k = q % 3;
-        double* buf = LDS_IR ? ir_lds + (int64_t)q * kSerYearCap : scratch + (int64_t)q * nd;
+        // the lane's samples: its LDS row holds kSerYearCap of them; past that they are only
+        // counted here, and such a year (intraday dates) is collected again, into the lane's
+        // scratch row [nd], below
+        double* const big = scratch + (int64_t)q * nd;
+        double* const small = LDS_IR ? ir_lds + (int64_t)q * kSerYearCap : big;
         int64_t n = 0;
         for (int64_t i0 = 0; i0 < nd; i0 += kSerB) {
             double xb[kSerB];
@@ -1024,23 +1029,37 @@ __global__ __launch_bounds__(1024) void xs_series_kernel(int64_t nd, const doubl
             }
 #pragma unroll
             for (int j = 0; j < kSerB; ++j)
-                if (i0 + j < nd && yb[j] == year0 + y && xb[j] == xb[j]) buf[n++] = xb[j];
-        }
-        double res = qnan();
-        if (n > 0) {
-            const double mean = seq_np_sum(buf, n) / (double)n;
-            double sd = qnan();
-            if (n > 1) {
-                const double avg = seq_np_sum(buf, n) / (double)n;
-                for (int64_t i = 0; i < n; ++i) {
-                    const double d = avg - buf[i];
-                    buf[i] = d * d;
+                if (i0 + j < nd && yb[j] == year0 + y && xb[j] == xb[j]) {
+                    if (!LDS_IR || n < kSerYearCap) small[n] = xb[j];
+                    ++n;
                 }
-                sd = __builtin_sqrt(seq_np_sum(buf, n) / ((double)n - 1.0));
-            }
-            res = mean / sd;
         }
-        ir[y * 3 + k] = res;
+        const bool spilled = LDS_IR && n > kSerYearCap;
+        if (spilled) {
+            n = 0;
+            for (int64_t i = 0; i < nd; ++i) {
+                const double x = ic[i * 3 + k];
+                if (year[i] == year0 + y && x == x) big[n++] = x;
+            }
+        }
+        auto mean_over_std = [n](double* buf) {            // (one copy per address space)
+            double res = qnan();
+            if (n > 0) {
+                const double mean = seq_np_sum(buf, n) / (double)n;
+                double sd = qnan();
+                if (n > 1) {
+                    const double avg = seq_np_sum(buf, n) / (double)n;
+                    for (int64_t i = 0; i < n; ++i) {
+                        const double d = avg - buf[i];
+                        buf[i] = d * d;
+                    }
+                    sd = __builtin_sqrt(seq_np_sum(buf, n) / ((double)n - 1.0));
+                }
+                res = mean / sd;
+            }
+            return res;
+        };
+        ir[y * 3 + k] = LDS_IR && !spilled ? mean_over_std(small) : mean_over_std(big);
     }
 }
 
@@ -1252,7 +1271,8 @@ extern "C" int afm_xs_series_f64(afm_ctx* ctx, int64_t nd, const double* layer_m
     AFM_CHECK_ARG(layer_mean && port && ic && year && cum_layer && ls && cum_port && ir &&
                       scratch, "null buffer");
     if (nd <= 0) return AFM_OK;
-    // the per-year IC samples in LDS when they fit (at most kSerYearCap dates a year)
+    // the per-year IC samples in LDS when the years' rows fit (kSerYearCap samples each; a
+    // longer year goes to scratch inside the kernel)
     const size_t lds = sizeof(double) * (size_t)(3 * nyears) * kSerYearCap;
     if (lds <= 150 * 1024) {
         AFM_HIP(afm_lds_opt_in(ctx, (const void*)xs_series_kernel<true>, 150 * 1024));

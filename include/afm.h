@@ -303,7 +303,8 @@ int afm_xs_stats_f64(afm_ctx* ctx, int64_t T, int64_t lda, const int32_t* dates,
                      int32_t* layer_cnt, double* port);
 /* Cumulative layers [nd][3][10], long-short [nd][3][5] (cum[10-l+1] - cum[l]), cumulative
  * top-10 returns [nd][3], IR [nyears][3] (year[nd] DEVICE int32, years year0..year0+nyears-1);
- * scratch [3*nyears][nd]. */
+ * scratch [3*nyears][nd].  A year may hold any number of the nd dates (minute bars: thousands);
+ * nyears <= 320. */
 int afm_xs_series_f64(afm_ctx* ctx, int64_t nd, const double* layer_mean, const double* port,
                       const double* ic, const int32_t* year, int nyears, int year0,
                       double* cum_layer, double* ls, double* cum_port, double* ir,

@@ -178,9 +178,11 @@ def layers(date, vals, k: int):
             (np.array(sd), np.array(sl, dtype=np.int64), np.array(sv, dtype=np.float64)))
 
 
-# string-rank pivot column order (KKT:362-365): '1.0','10.0','2.0',...,'9.0'
-_PIVOT_ORDER = sorted([f"{float(r)}" for r in range(1, TOP_K + 1)])
-PIVOT_RANKS = np.array([int(float(s)) for s in _PIVOT_ORDER])
+def pivot_ranks(m: int) -> np.ndarray:
+    """The pivot's columns (KKT:362-365): the ranks 1..m that some date holds, as strings, in
+    string order -- '1.0','10.0','2.0',...,'9.0' for m = 10, 1..m below."""
+    return np.array([int(float(s)) for s in sorted(f"{float(r)}" for r in range(1, m + 1))],
+                    dtype=np.int64)
 
 
 def _row_sum(row: np.ndarray) -> float:
@@ -189,15 +191,17 @@ def _row_sum(row: np.ndarray) -> float:
 
 
 def top_stocks(date, vals):
-    """KKT:356-373: factor-weighted top-10 by descending rank, per return type + cumsum."""
+    """KKT:356-373: factor-weighted top-10 by descending rank, per return type + cumsum.  The
+    pivot has a column per rank that some date holds: m = min(10, the most rows of a date)."""
     off = group_starts(date)
     nd = len(off) - 1
     res = np.zeros((nd, len(RETURN_TYPES)))
+    ranks = pivot_ranks(min(TOP_K, int(np.diff(off).max())) if nd else 0)
     for g in range(nd):
         s, e = off[g], off[g + 1]
         rk = rank_first(vals[s:e, 0], ascending=False)
-        piv = np.full((len(RETURN_TYPES) + 1, TOP_K), np.nan)
-        for c, r in enumerate(PIVOT_RANKS):
+        piv = np.full((len(RETURN_TYPES) + 1, len(ranks)), np.nan)
+        for c, r in enumerate(ranks):
             hit = np.flatnonzero(rk == r)
             if len(hit):
                 piv[:, c] = vals[s + hit[0], :]

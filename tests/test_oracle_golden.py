@@ -145,3 +145,20 @@ def test_np_sum_matches_numpy_buffered_reduce():
                                             f"from the 8192-chunk model", n, scale)
             sparse = np.where(rng.random(n) < 0.004, np.abs(v), 0.0)   # a turnover vector
             assert np_sum(sparse) == np.sum(sparse), (n, scale)
+
+
+@pytest.mark.parametrize("counts", [[9] * 6, [7] * 6, [3, 5, 9, 8], [8, 8], [3, 12, 9, 10, 11],
+                                    [1, 2], [10] * 4], ids=lambda c: "-".join(map(str, c)))
+def test_top_stocks_matches_pandas_pivot(counts):
+    """xs.top_stocks against the statements of KKT:358-369 run in pandas, on panels where no date
+    has ten rows: the pivot then holds only the ranks 1..m that exist (columns '1.0'..'m.0'), and
+    numpy's 8-accumulator row sum groups m terms differently from ten with NaN -> 0."""
+    from analyzer_ref import top_stocks_pandas
+    nd = len(counts)
+    date = np.repeat(np.arange(nd), counts)
+    for seed in range(25):
+        rng = np.random.default_rng(seed)
+        vals = np.column_stack([rng.normal(size=len(date))] +
+                               [0.02 * rng.normal(size=len(date)) for _ in range(3)])
+        _, _, v = xs.top_stocks(date, vals)
+        assert same(v.reshape(nd, 6)[:, :3], top_stocks_pandas(date, vals)), seed
