@@ -1,4 +1,4 @@
-"""ctypes binding of libafm.so (the C-ABI declared in include/afm.h).
+"""ctypes binding of libafm.so (the C-ABI declared in include/afm.h and include/afm_mv.h).
 
 The product path has no CPU fallback: if the library is missing or no GPU is visible, every
 call raises.  ``make -C alpha-multi-factor-models_amd`` (or ``__graft_entry__.build()``) builds
@@ -98,6 +98,15 @@ SIGNATURES = {
                                       "f64*"),
     "afm_gram_score_f64": ("status", "ctx f64* i64 f64* i64 int f64* int i64 f64*"),
 }
+# the same for include/afm_mv.h, the mean-variance entry points (tests/test_abi_mv.py)
+SIGNATURES_MV = {
+    "afm_rebalance_mv_f64": ("status", "ctx i64 i64 i64 i32* i64 f64* i64* f64* i64* i64 i64 i64 "
+                                       "f64* f64* int f64 f64 f64* f64 i32* i32* f64* f64* i32* "
+                                       "i64* i32*"),
+    "afm_mean_variance_weights_f64": ("status", "ctx f64* i64 i64 int f64* f64 f64 f64 f64* f64* "
+                                                "i32*"),
+}
+TABLES = (SIGNATURES, SIGNATURES_MV)
 _RESTYPE = {"status": I32, "int": I32, "i64": I64, "str": ctypes.c_char_p}
 _ARGTYPE = {"int": I32, "i64": I64, "f64": DBL, "str": ctypes.c_char_p}    # every pointer: void*
 
@@ -119,10 +128,11 @@ def lib():
                     raise ImportError(f"{LIB_PATH} is not built: run `make -C "
                                       f"{os.path.dirname(HERE)}` (hipcc, gfx950)")
                 L = ctypes.CDLL(LIB_PATH)
-                for name, (res, params) in SIGNATURES.items():
-                    f = getattr(L, name)
-                    f.restype = _RESTYPE[res]
-                    f.argtypes = [_ARGTYPE.get(t, P) for t in params.split()]
+                for table in TABLES:
+                    for name, (res, params) in table.items():
+                        f = getattr(L, name)
+                        f.restype = _RESTYPE[res]
+                        f.argtypes = [_ARGTYPE.get(t, P) for t in params.split()]
                 _lib = L
     return _lib
 
@@ -156,14 +166,15 @@ def _device_buffer(dtype, device: int, where: str):
 
 def _plans(device: int) -> dict:
     """name -> (takes the context, one converter per further parameter, failed(return value)):
-    how Context.call marshals each entry point of SIGNATURES for the context of ``device``."""
+    how Context.call marshals each entry point of SIGNATURES and SIGNATURES_MV for the context of
+    ``device``."""
     import torch
     scalar = {"int": operator.index, "i64": operator.index, "f64": float}
     buffer = {"f64*": torch.float64, "i32*": torch.int32, "i64*": torch.int64}
     negative = (0).__gt__
     failed = {"status": bool, "int": negative, "i64": negative, "str": lambda s: s is None}
     plans = {}
-    for name, (res, params) in SIGNATURES.items():
+    for name, (res, params) in (item for table in TABLES for item in table.items()):
         toks = params.split()
         takes_ctx = toks[:1] == ["ctx"]
         convs = tuple(_device_buffer(buffer[t], device, f"{name} argument {i}") if t in buffer

@@ -94,6 +94,11 @@ class PipelineConfig:
     window: int | None = 252        # rolling covariance window (north star); None = KKT:858
     lo: float = 0.0                 # KKT:828
     hi: float = 0.1
+    # the return term of the weight solve: min 1/2 w'Sw - risk_tolerance * s * mu'w (s = -1 for
+    # the short book); 0 = the min-variance solve.  expected: "prediction" (mu = the step's
+    # predictions) or "history" (the members' means over the covariance window, KKT:821)
+    risk_tolerance: float = 0.0
+    expected: str = "prediction"
     rate: float = 1e-4              # KKT:796
     v0: float = 100000000.0         # KKT:804
     tol: float = 1e-10              # pivot threshold of the per-date solve
@@ -774,7 +779,16 @@ class Pipeline:
         if W > 1:
             self.main.wait_event(self.labels_done)     # the label planes
         x, ne = self.reb_ext, self.e1 - self.e0
-        if ne > 0:
+        if ne > 0 and c.risk_tolerance != 0:
+            if c.expected not in ("prediction", "history"):
+                raise ValueError(f"expected={c.expected!r}: expected prediction or history")
+            self.ctx.call("afm_rebalance_mv_f64", self.T, full.A, full.lda, self.rd_ext, ne,
+                          self.pred, full.tbits, self.target, self.zrows_full, 0, sp.tr1,
+                          -1 if c.window is None else int(c.window), full.close, self.tmr,
+                          c.top_n, c.lo, c.hi, self.pred if c.expected == "prediction" else None,
+                          c.risk_tolerance, x["k"], x["books"], x["weights"], x["sums"],
+                          x["upos"], x["usize"], x["status"])
+        elif ne > 0:
             self.ctx.call("afm_rebalance_f64", self.T, full.A, full.lda, self.rd_ext, ne,
                           self.pred, full.tbits, self.target, self.zrows_full, 0, sp.tr1,
                           -1 if c.window is None else int(c.window), full.close, self.tmr,

@@ -13,7 +13,10 @@ Differences from the reference, by design:
 * equal predictions are ordered by ascending security id (the reference: Python set order).
 Extensions: ``window`` (rolling history window in dates; None = the reference's whole history),
 ``books`` (the long/short ids per date -- the reference's ``positions`` stays all-NaN because its
-chained assignment at KKT:890-891 never writes).
+chained assignment at KKT:890-891 never writes), ``risk_tolerance`` / ``expected`` (the
+mean-variance solve: min 1/2 w'Sw - risk_tolerance * s * mu'w with mu the predictions or the
+history mean the reference computes and drops at KKT:821, s = -1 for the short book; 0 = the
+min-variance solve above).
 """
 from __future__ import annotations
 
@@ -31,11 +34,20 @@ def _dev():
 
 
 def rebalance(pred, trad_bits, hist, hist_bits, close, tmr, dates_idx, *, A: int, top_n: int = 10,
-              window: int | None = None, h_range=None, lo: float = 0.0, hi: float = 0.1):
+              window: int | None = None, h_range=None, lo: float = 0.0, hi: float = 0.1,
+              risk_tolerance: float = 0.0, mu=None):
     """Device-level K1-K3 for the grid panel.  All arrays torch CUDA tensors ([T][lda] planes,
     [ceil(T/64)][lda] bit words); ``dates_idx`` int32 grid indices of the rebalance dates.
+    ``risk_tolerance`` > 0: the mean-variance solve with ``mu`` a [T][lda] device plane of expected
+    returns (the prediction plane, say) or "history" (the members' history-window means).
     Returns a dict of device tensors (k, books, weights, sums, upos, usize, status)."""
     import torch
+    if risk_tolerance != 0 and mu is None:
+        raise ValueError("risk_tolerance needs mu: a [T][lda] device plane or \"history\"")
+    if isinstance(mu, str) and mu != "history":
+        raise ValueError(f"mu must be a device plane or \"history\", not {mu!r}")
+    if mu is not None and not isinstance(mu, str) and tuple(mu.shape) != tuple(pred.shape):
+        raise ValueError("the mu plane must have the shape of pred")
     dev = pred.device
     T, lda = pred.shape
     nd = int(dates_idx.numel())
@@ -49,10 +61,17 @@ def rebalance(pred, trad_bits, hist, hist_bits, close, tmr, dates_idx, *, A: int
         "status": torch.empty(nd, dtype=torch.int32, device=dev),
     }
     h0, h1 = h_range if h_range is not None else (0, T)
-    _lib.run("afm_rebalance_f64", T, A, lda, dates_idx, nd, pred, trad_bits, hist, hist_bits, h0,
-             h1, -1 if window is None else int(window), close, tmr, int(top_n), float(lo),
-             float(hi), out["k"], out["books"], out["weights"], out["sums"], out["upos"],
-             out["usize"], out["status"])
+    if risk_tolerance == 0:
+        _lib.run("afm_rebalance_f64", T, A, lda, dates_idx, nd, pred, trad_bits, hist, hist_bits,
+                 h0, h1, -1 if window is None else int(window), close, tmr, int(top_n), float(lo),
+                 float(hi), out["k"], out["books"], out["weights"], out["sums"], out["upos"],
+                 out["usize"], out["status"])
+    else:
+        _lib.run("afm_rebalance_mv_f64", T, A, lda, dates_idx, nd, pred, trad_bits, hist,
+                 hist_bits, h0, h1, -1 if window is None else int(window), close, tmr, int(top_n),
+                 float(lo), float(hi), None if isinstance(mu, str) else mu, float(risk_tolerance),
+                 out["k"], out["books"], out["weights"], out["sums"], out["upos"], out["usize"],
+                 out["status"])
     return out
 
 
@@ -115,12 +134,46 @@ def min_variance_weights(returns, lo: float = 0.0, hi: float = 0.1):
     return w.cpu().numpy(), cov.cpu().numpy()
 
 
+def mean_variance_weights(returns, mu=None, risk_tolerance: float = 0.0, lo: float = 0.0,
+                          hi: float = 0.1, status: bool = False):
+    """One book with the return term: min 1/2 w'Sw - risk_tolerance * mu'w, sum w = 1,
+    lo <= w <= hi.  returns [rows][k] (NaN = missing); ``mu`` [k] expected returns (non-finite
+    counts as 0) or None = the columns' means over their finite rows -> (w[k], cov[k][k]), and with
+    ``status`` the solve's status word (0 ok, 1 iteration cap or a non-finite covariance)."""
+    import torch
+    R = torch.as_tensor(np.ascontiguousarray(np.asarray(returns, dtype=np.float64)),
+                        device=_dev())
+    if R.ndim != 2:
+        raise ValueError("returns must be 2-D [dates x assets]")
+    rows, k = R.shape
+    if k > MAX_BOOK:
+        raise ValueError(f"book of {k} > {MAX_BOOK} names")
+    m = None
+    if mu is not None:
+        m = torch.as_tensor(np.ascontiguousarray(np.asarray(mu, dtype=np.float64)),
+                            device=R.device)
+        if tuple(m.shape) != (k,):
+            raise ValueError(f"mu must have one value per column ({k})")
+    w = torch.empty(k, dtype=torch.float64, device=R.device)
+    cov = torch.empty((k, k), dtype=torch.float64, device=R.device)
+    st = torch.empty(1, dtype=torch.int32, device=R.device)
+    _lib.run("afm_mean_variance_weights_f64", R, rows, k, k, m, float(risk_tolerance), float(lo),
+             float(hi), w, cov, st)
+    if status:
+        return w.cpu().numpy(), cov.cpu().numpy(), int(st.item())
+    return w.cpu().numpy(), cov.cpu().numpy()
+
+
 class PortfolioManager:
     """Drop-in for ``PortfolioManager`` (KKT:795-970)."""
 
     def __init__(self, predictions, history, all_df, trading_cost_rate=0.0001, top_n=10,
-                 window=None, lo=0.0, hi=0.1):
+                 window=None, lo=0.0, hi=0.1, risk_tolerance=0.0, expected="prediction"):
         import pandas as pd
+        if expected not in ("prediction", "history"):
+            raise ValueError("expected must be \"prediction\" or \"history\"")
+        self.risk_tolerance = risk_tolerance
+        self.expected = expected
         self.predictions = predictions
         self.predictions.index.names = ["date", "id"]              # KKT:798
         self.history = history
@@ -142,9 +195,18 @@ class PortfolioManager:
         return np.sqrt(np.dot(weights.T, np.dot(cov_matrix, weights)))
 
     def determine_weights(self, returns):                                # KKT:817-833
-        w, _ = min_variance_weights(returns.to_numpy(np.float64) if hasattr(returns, "to_numpy")
-                                    else returns, self.lo, self.hi)
-        return w
+        R = returns.to_numpy(np.float64) if hasattr(returns, "to_numpy") else returns
+        if self.risk_tolerance != 0:     # mu = returns.mean(), the reference's mean_returns
+            return mean_variance_weights(R, None, self.risk_tolerance, self.lo, self.hi)[0]
+        return min_variance_weights(R, self.lo, self.hi)[0]
+
+    def _rebalance(self, g):
+        mu = None
+        if self.risk_tolerance != 0:
+            mu = g["pred"] if self.expected == "prediction" else "history"
+        return rebalance(g["pred"], g["tbits"], g["hist"], g["hbits"], g["close"], g["tmr"],
+                         g["rdates"], A=g["A"], top_n=self.top_n, window=self.window, lo=self.lo,
+                         hi=self.hi, risk_tolerance=self.risk_tolerance, mu=mu)
 
     def _grid(self):
         import torch
@@ -185,9 +247,7 @@ class PortfolioManager:
     def calculate_portfolio(self):                                       # KKT:842-892
         import pandas as pd
         g = self._grid()
-        reb = rebalance(g["pred"], g["tbits"], g["hist"], g["hbits"], g["close"], g["tmr"],
-                        g["rdates"], A=g["A"], top_n=self.top_n, window=self.window, lo=self.lo,
-                        hi=self.hi)
+        reb = self._rebalance(g)
         res = pnl_scan(reb, V0, self.trading_cost_rate)
         st = reb["status"].cpu().numpy()
         if (st == 2).any():
@@ -227,9 +287,7 @@ class PortfolioManager:
         Returns (paths [n_paths][steps] indices into the sorted rebalance dates, dict of numpy
         arrays value [n_paths][steps+1], turnover, long_ret, short_ret [n_paths][steps])."""
         g = self._grid()
-        reb = rebalance(g["pred"], g["tbits"], g["hist"], g["hbits"], g["close"], g["tmr"],
-                        g["rdates"], A=g["A"], top_n=self.top_n, window=self.window, lo=self.lo,
-                        hi=self.hi)
+        reb = self._rebalance(g)
         nd = int(reb["k"].numel())
         if paths is None:
             paths = bootstrap_paths(nd, n_paths, steps, seed)

@@ -13,7 +13,8 @@
 //   4. min w'Sw  s.t. sum w = 1, lo <= w <= hi (KKT:811-833) solved EXACTLY by a primal
 //      active-set method: each step solves the KKT system [S_FF 1; 1' 0][w_F; lam] by an LDS
 //      Cholesky of S_FF and the Schur complement of the equality (SLSQP is not a parity target,
-//      SURVEY.md §0 F6);
+//      SURVEY.md §0 F6); the mean-variance instantiations (afm_rebalance_mv_f64, include/afm_mv.h)
+//      minimise 1/2 w'Sw - gamma s mu'w instead, mu the predictions or the history window's mean;
 //   5. per book: sum(tmr * w) as numpy's pairwise sum (Series.sum, KKT:875-877) and
 //      sum(w * close) as Python's sequential builtin sum (KKT:881-882); the members' positions
 //      in the id-union of this and the neighbouring rebalance dates' prediction sets (the
@@ -22,8 +23,10 @@
 //   (KKT:864-892), turnover = numpy pairwise sum over the aligned union vector (zeros and NaN
 //   -> 0 included, evaluated sparsely at the members' union positions).
 #include "afm_internal.h"
+#include "afm_mv.h"
 
 #include <algorithm>
+#include <cmath>
 #include <type_traits>
 #include <vector>
 
@@ -65,6 +68,9 @@ struct RebArgs {
     int32_t* upos;            // [nd][2][2][kMaxK]: union position vs prev / vs next (-1 absent)
     int64_t* usize;           // [nd][2]: |P_prev U P_i|, |P_i U P_next|
     int32_t* status;          // [nd] (zeroed by the launcher): |1 QP iteration cap, 2 k > cap
+    // the return term of the mean-variance instantiations (afm_rebalance_mv_f64; unread otherwise)
+    const double* mu;         // [T][lda] expected returns, or null: the history window's mean
+    double gamma;             // risk tolerance
 };
 
 __device__ __forceinline__ u64 okey(double v) {   // order-preserving key, -0.0 == +0.0
@@ -143,6 +149,41 @@ struct Shared {
 
 static_assert(sizeof(Shared<kMaxK>) <= 160 * 1024, "rebalance LDS over the CU's 160 KB");
 static_assert(sizeof(Shared<32>) <= 40 * 1024, "headline rebalance LDS: 4 workgroups per CU");
+
+// LDS of the mean-variance instantiations: the same layout, then the book's linear term
+// gm = gamma * s * mu (s = -1 for the short book).  The min-variance kernels keep Shared<KM>.
+template <int KM>
+struct SharedMV : Shared<KM> {
+    double gm[KM];
+};
+
+static_assert(sizeof(SharedMV<kMaxK>) <= 160 * 1024, "mean-variance LDS over the CU's 160 KB");
+static_assert(sizeof(SharedMV<32>) <= 40 * 1024, "mean-variance LDS: 4 workgroups per CU");
+
+// gm[m] = gs * (mean of member m's finite history rows [0, rows)), 0 for a member without any
+// (KKT:821 mean_returns).  kT / KM threads per member, each summing its rows p, p + G, ... in
+// order; the partial sums meet in a butterfly (the same additions in every lane): a fixed order.
+template <int KM, class Get>
+__device__ __forceinline__ void book_gm_history(double* gm, const int k, const int64_t rows,
+                                                const double gs, Get get) {
+    constexpr int G = kT / KM;
+    static_assert(G >= 1 && (G & (G - 1)) == 0 && G <= 64, "threads per member: a power of two");
+    const int tid = threadIdx.x, m = tid / G, p = tid % G;
+    double s = 0.0;
+    int n = 0;
+    if (m < k) {
+        for (int64_t row = p; row < rows; row += G) {
+            const double v = get(m, row);
+            if (__builtin_isfinite(v)) { s = s + v; ++n; }
+        }
+    }
+    for (int o = G / 2; o >= 1; o >>= 1) {
+        s = s + __shfl_xor(s, o, 64);
+        n += __shfl_xor(n, o, 64);
+    }
+    if (m < k && p == 0) gm[m] = n > 0 ? gs * (s / (double)n) : 0.0;
+    __syncthreads();
+}
 
 // Welford pairwise-complete covariance (pandas nancorr(cov=True), KKT:821-822: rows in date
 // order, a pair's rows where both values are finite) of the k members' history rows [0, rows)
@@ -559,7 +600,11 @@ __device__ __forceinline__ bool select_top_reg(Shared<KM>& sh, const u64 (&ks)[K
     return true;
 }
 
-// numpy pairwise sum of a dense vector (n small)
+// numpy pairwise sum of a dense vector (n small).  MV: a copy of its own for the mean-variance
+// kernels, so that they add no caller to the min-variance kernels' copy (which the compiler
+// inlines there: with more callers it would call it out of line, at the cost of registers and
+// a stack in the headline kernel).
+template <bool MV = false>
 __device__ double pairwise_dense(const double* a, int n) {
     if (n < 8) {
         double res = 0.;
@@ -577,7 +622,7 @@ __device__ double pairwise_dense(const double* a, int n) {
     }
     int n2 = n / 2;
     n2 -= n2 % 8;
-    return pairwise_dense(a, n2) + pairwise_dense(a + n2, n - n2);
+    return pairwise_dense<MV>(a, n2) + pairwise_dense<MV>(a + n2, n - n2);
 }
 
 // ---- wave-level helpers of the QP (wave 0 runs it alone: no workgroup barrier inside) --------
@@ -675,12 +720,83 @@ __device__ __forceinline__ bool qp_setup(Shared<KM>& sh, const int n) {
     return true;
 }
 
+// Bordering of qp_wave by member j: u = M s (s = S[F][j]), d = S_jj - s'u; j joins the free list
+// (oq: the lanes' free-list members, nf: the free count, advanced).
+template <int KM>
+__device__ __forceinline__ void qp_wave_border(Shared<KM>& sh, const int j,
+                                               const int (&oq)[(KM + 63) / 64], int& nf) {
+    constexpr int R = (KM + 63) / 64;
+    const int lane = threadIdx.x & 63;
+    double* M = sh.u.L;
+    double sv[R], u[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        sv[r] = lane + 64 * r < nf ? sh.S[tri(oq[r], j)] : 0.0;
+        u[r] = 0.0;
+    }
+#pragma unroll
+    for (int rb = 0; rb < R; ++rb) {
+        const int lim = nf - 64 * rb < 64 ? nf - 64 * rb : 64;
+#pragma unroll 4
+        for (int lb = 0; lb < lim; ++lb) {
+            const int qb = __builtin_amdgcn_readlane(oq[rb], lb);
+            const double sb = rdlane(sv[rb], lb);
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                if (lane + 64 * r < nf) u[r] = u[r] + M[tri(oq[r], qb)] * sb;
+        }
+    }
+    double su = 0.0;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+        if (lane + 64 * r < nf) su += sv[r] * u[r];
+    const double d = sh.S[tri(j, j)] - wave_sum(su);
+    const double rd = 1.0 / d;
+    double ua[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) ua[r] = u[r] * rd;
+#pragma unroll
+    for (int rb = 0; rb < R; ++rb) {
+        const int lim = nf - 64 * rb < 64 ? nf - 64 * rb : 64;
+#pragma unroll 4
+        for (int lb = 0; lb < lim; ++lb) {
+            const int b = 64 * rb + lb;
+            const int qb = __builtin_amdgcn_readlane(oq[rb], lb);
+            const double ub = rdlane(u[rb], lb);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if (lane + 64 * r < nf && lane + 64 * r >= b) {
+                    const int e = tri(oq[r], qb);
+                    M[e] = M[e] + ua[r] * ub;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+        if (lane + 64 * r < nf) M[tri(oq[r], j)] = -ua[r];
+    if (lane == 0) {
+        M[tri(j, j)] = rd;
+        sh.ord[nf] = j;
+        sh.state[j] = 0;
+    }
+    lds_sync();
+    ++nf;
+}
+
 // The iterations, on wave 0 alone (no workgroup barrier inside): lanes own free-list
 // positions a = lane + 64 r (sh.ord[a] = member).  Returns true if the iteration cap was hit
 // (uniform in wave 0).
-template <int KM>
+//
+// MV (the mean-variance instantiation): min 1/2 w'Sw - gm'w with gm = gamma * s * mu in LDS.  The
+// step's right-hand side becomes c = S_FB w_B - gm_F and a bound member's multiplier
+// g = S w - gm + lam; a fully bound vertex (no free member -- the common optimum once the return
+// term outweighs the risk term) is tested on its own: see the nf == 0 branch.
+template <int KM, bool MV = false>
 __device__ __forceinline__ bool qp_wave(Shared<KM>& sh, const int n, const double lo,
                                         const double hi) {
+    [[maybe_unused]] const double* gm = nullptr;       // MV: sh is the base of a SharedMV
+    if constexpr (MV) gm = static_cast<SharedMV<KM>&>(sh).gm;
     constexpr int R = (KM + 63) / 64;
     const int lane = threadIdx.x & 63;
     double* M = sh.u.L;
@@ -689,7 +805,42 @@ __device__ __forceinline__ bool qp_wave(Shared<KM>& sh, const int n, const doubl
     bool capped = false;
     const int max_it = 4 * n + 8;
     for (int it = 0; it < max_it; ++it) {
-        if (nf == 0) break;
+        if constexpr (MV) {
+            if (nf == 0) {
+                // fully bound vertex: g = S w - gm; i = argmax g over the members at hi,
+                // j = argmin g over those at lo (ties: ascending index).  Moving mass from i to j
+                // descends iff g_i > g_j: then both are released (i, then j), else the vertex is
+                // the optimum.
+                double vhi = __builtin_inf(), vlo = __builtin_inf();
+                int qhi = 0x7fffffff, qlo = 0x7fffffff;
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const int q = lane + 64 * r;
+                    if (q < n) {
+                        double g = 0.0;
+#pragma unroll 4
+                        for (int b = 0; b < n; ++b) g = g + sh.S[tri(q, b)] * sh.w[b];
+                        g = g - gm[q];
+                        if (sh.state[q] > 0) {
+                            if (-g < vhi) { vhi = -g; qhi = q; }
+                        } else if (g < vlo) { vlo = g; qlo = q; }
+                    }
+                }
+                wave_argmin(vhi, qhi);
+                wave_argmin(vlo, qlo);
+                if (qhi == 0x7fffffff || qlo == 0x7fffffff || !(-vhi > vlo)) break;
+                if (it == max_it - 1) capped = true;
+                int oq[R];
+#pragma unroll
+                for (int r = 0; r < R; ++r) oq[r] = 0;
+                qp_wave_border(sh, qhi, oq, nf);       // nf = 0: M = [1 / S_ii]
+                oq[0] = lane < 1 ? qhi : 0;
+                qp_wave_border(sh, qlo, oq, nf);
+                continue;
+            }
+        } else {
+            if (nf == 0) break;
+        }
         if (it == max_it - 1) capped = true;
         int oq[R];
         double bs = 0.0;
@@ -716,6 +867,7 @@ __device__ __forceinline__ bool qp_wave(Shared<KM>& sh, const int n, const doubl
                     const int q = blist[i];
                     cc = cc + sh.S[tri(q, oq[r])] * sh.w[q];
                 }
+                if constexpr (MV) cc = cc - gm[oq[r]];
             }
             cpos[r] = cc;
         }
@@ -769,6 +921,7 @@ __device__ __forceinline__ bool qp_wave(Shared<KM>& sh, const int n, const doubl
                     double g = 0.0;
 #pragma unroll 4
                     for (int b = 0; b < n; ++b) g = g + sh.S[tri(q, b)] * sh.w[b];
+                    if constexpr (MV) g = g - gm[q];
                     g = g + lam;
                     const double v = sh.state[q] < 0 ? g : -g;
                     if (v < vmin) { vmin = v; qmin = q; }
@@ -776,62 +929,7 @@ __device__ __forceinline__ bool qp_wave(Shared<KM>& sh, const int n, const doubl
             }
             wave_argmin(vmin, qmin);
             if (!(vmin < 0.0)) break;
-            // bordering: u = M s (s = S[F][qmin]), d = S_jj - s'u
-            const int j = qmin;
-            double sv[R], u[R];
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                sv[r] = lane + 64 * r < nf ? sh.S[tri(oq[r], j)] : 0.0;
-                u[r] = 0.0;
-            }
-#pragma unroll
-            for (int rb = 0; rb < R; ++rb) {
-                const int lim = nf - 64 * rb < 64 ? nf - 64 * rb : 64;
-#pragma unroll 4
-                for (int lb = 0; lb < lim; ++lb) {
-                    const int qb = __builtin_amdgcn_readlane(oq[rb], lb);
-                    const double sb = rdlane(sv[rb], lb);
-#pragma unroll
-                    for (int r = 0; r < R; ++r)
-                        if (lane + 64 * r < nf) u[r] = u[r] + M[tri(oq[r], qb)] * sb;
-                }
-            }
-            double su = 0.0;
-#pragma unroll
-            for (int r = 0; r < R; ++r)
-                if (lane + 64 * r < nf) su += sv[r] * u[r];
-            const double d = sh.S[tri(j, j)] - wave_sum(su);
-            const double rd = 1.0 / d;
-            double ua[R];
-#pragma unroll
-            for (int r = 0; r < R; ++r) ua[r] = u[r] * rd;
-#pragma unroll
-            for (int rb = 0; rb < R; ++rb) {
-                const int lim = nf - 64 * rb < 64 ? nf - 64 * rb : 64;
-#pragma unroll 4
-                for (int lb = 0; lb < lim; ++lb) {
-                    const int b = 64 * rb + lb;
-                    const int qb = __builtin_amdgcn_readlane(oq[rb], lb);
-                    const double ub = rdlane(u[rb], lb);
-#pragma unroll
-                    for (int r = 0; r < R; ++r) {
-                        if (lane + 64 * r < nf && lane + 64 * r >= b) {
-                            const int e = tri(oq[r], qb);
-                            M[e] = M[e] + ua[r] * ub;
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < R; ++r)
-                if (lane + 64 * r < nf) M[tri(oq[r], j)] = -ua[r];
-            if (lane == 0) {
-                M[tri(j, j)] = rd;
-                sh.ord[nf] = j;
-                sh.state[j] = 0;
-            }
-            lds_sync();
-            ++nf;
+            qp_wave_border(sh, qmin, oq, nf);
         } else {
             // ratio test: the first member (ascending index) to hit its bound along x - w
             double amin = __builtin_inf();
@@ -971,9 +1069,46 @@ __device__ __forceinline__ bool mbit(const u64 (&m)[2], int b) {
     return (m[b >> 6] >> (b & 63)) & 1ull;
 }
 
+// Bordering of qp_block by member j (uniform; fj: this thread's member is free): s = S[.][j],
+// u = M s, d = S_jj - s'u; j leaves the bound masks.  The vertex step of the mean-variance
+// instantiation borders twice through this copy; the release step of qp_block keeps the same
+// statements inline, where the min-variance instantiation compiles to the code it always had.
 template <int KM>
+__device__ __forceinline__ void qp_block_border(Shared<KM>& sh, double (&Mr)[64], u64 (&bnd)[2],
+                                                u64 (&bhi)[2], int& nf, const int n, const int j,
+                                                const bool fj) {
+    QpLds& q = sh.u.qp;
+    const int a = threadIdx.x & 127;
+    const int h = __builtin_amdgcn_readfirstlane(threadIdx.x >> 7), b0 = 64 * h;
+    double up = 0.0;
+#pragma unroll
+    for (int i = 0; i < 64; ++i) {
+        const int b = b0 + i;
+        up = __builtin_fma(Mr[i], b < n ? sh.S[tri(j, b)] : 0.0, up);
+    }
+    q.part[3][h][a] = up;
+    __syncthreads();
+    const double ua = q.part[3][0][a] + q.part[3][1][a];    // 0 off the free set
+    double su = h == 0 && fj ? sh.S[tri(a, j)] * ua : 0.0, z1 = 0.0, z2 = 0.0;
+    blk_sum3(q.red[1], su, z1, z2);
+    const double rd = 1.0 / (sh.S[tri(j, j)] - su);
+    const double ut = a == j ? -1.0 : ua;
+    if (h == 0) q.vu[a] = ut;
+    __syncthreads();
+    const double utr = ut * rd;
+#pragma unroll
+    for (int i = 0; i < 64; ++i) Mr[i] = __builtin_fma(utr, q.vu[b0 + i], Mr[i]);
+    bnd[j >> 6] &= ~(1ull << (j & 63));
+    bhi[j >> 6] &= ~(1ull << (j & 63));
+    ++nf;
+}
+
+// MV: the linear term gm and the vertex test, as in qp_wave.
+template <int KM, bool MV = false>
 __device__ __noinline__ bool qp_block(Shared<KM>& sh, const int n, const double lo,
                                      const double hi, int64_t* stamps) {
+    [[maybe_unused]] const double* gm = nullptr;       // MV: sh is the base of a SharedMV
+    if constexpr (MV) gm = static_cast<SharedMV<KM>&>(sh).gm;
     static_assert(KM == 128 && kT == 256, "qp_block: 128 member rows x 2 column halves");
     QpLds& q = sh.u.qp;
     // the column half is uniform per wave: column indices, their LDS addresses and the S row
@@ -1072,7 +1207,36 @@ __device__ __noinline__ bool qp_block(Shared<KM>& sh, const int n, const double 
     const int max_it = 4 * n + 8;
     int it = 0;
     for (; it < max_it; ++it) {
-        if (nf == 0) break;
+        if constexpr (MV) {
+            if (nf == 0) {
+                // fully bound vertex (qp_wave): g = S w - gm, one member per thread of half 0
+                if (h == 0) q.vw[a] = wa;
+                __syncthreads();
+                double vhi = __builtin_inf(), vlo = __builtin_inf();
+                int qhi = 0x7fffffff, qlo = 0x7fffffff;
+                if (h == 0 && mem) {
+                    double g = 0.0;
+#pragma unroll 4
+                    for (int b = 0; b < n; ++b) g = g + sh.S[tri(a, b)] * q.vw[b];
+                    g = g - gm[a];
+                    if (mbit(bhi, a)) { vhi = -g; qhi = a; }
+                    else { vlo = g; qlo = a; }
+                }
+                blk_argmin(q, vhi, qhi);
+                __syncthreads();                       // the reduction slots are read: reuse them
+                blk_argmin(q, vlo, qlo);
+                if (qhi == 0x7fffffff || qlo == 0x7fffffff || !(-vhi > vlo)) break;
+                if (it == max_it - 1) capped = true;
+                const int ji = __builtin_amdgcn_readfirstlane(qhi);
+                const int jj = __builtin_amdgcn_readfirstlane(qlo);
+                // (nf = 0: M = e_i e_i' / S_ii)
+                qp_block_border(sh, Mr, bnd, bhi, nf, n, ji, false);
+                qp_block_border(sh, Mr, bnd, bhi, nf, n, jj, a == ji);
+                continue;
+            }
+        } else {
+            if (nf == 0) break;
+        }
         if (it == max_it - 1) capped = true;
         const bool ba = mem && mbit(bnd, a), fa = mem && !ba;
         // c = S_FB w_B and the bound weight sum, bound members in ascending order
@@ -1088,7 +1252,11 @@ __device__ __noinline__ bool qp_block(Shared<KM>& sh, const int n, const double 
                 if (h == 0) ca = ca + sh.S[tri(a, b)] * wb;
             }
         }
-        if (h == 0) q.vc[a] = fa ? ca : 0.0;
+        if constexpr (MV) {
+            if (h == 0) q.vc[a] = fa ? ca - gm[a] : 0.0;
+        } else {
+            if (h == 0) q.vc[a] = fa ? ca : 0.0;
+        }
         __syncthreads();
         double p1 = 0.0, p2 = 0.0;                     // y1 = M 1_F, y2 = M c
 #pragma unroll
@@ -1127,7 +1295,9 @@ __device__ __noinline__ bool qp_block(Shared<KM>& sh, const int n, const double 
                         const int b = lane + 64 * e;
                         if (b < n) g = g + sh.S[tri(j, b)] * q.vw[b];
                     }
-                    g = wave_sum(g) + lam;
+                    g = wave_sum(g);
+                    if constexpr (MV) g = g - gm[j];
+                    g = g + lam;
                     const double v = mbit(bhi, j) ? -g : g;
                     if (v < vmin) { vmin = v; jmin = j; }
                 }
@@ -1220,12 +1390,17 @@ __device__ __noinline__ bool qp_block(Shared<KM>& sh, const int n, const double 
 }
 
 // determine_weights for one book: [rows][ld] returns (k columns, NaN = missing) -> covariance
-// (an output) and weights
+// (an output) and weights.  MV: with the return term, mu [k] given or (null) the columns' means
+// over their finite rows (unread otherwise).
+template <bool MV>
 __global__ __launch_bounds__(kT) void weights_kernel(const double* R, int64_t rows, int64_t ld,
                                                      int k, double lo, double hi, double* w,
-                                                     double* cov, int32_t* status) {
+                                                     double* cov, int32_t* status,
+                                                     const double* mu, double gamma) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    Shared<kMaxK>& sh = *reinterpret_cast<Shared<kMaxK>*>(smem_raw);
+    using Lds = typename std::conditional<MV, SharedMV<kMaxK>, Shared<kMaxK>>::type;
+    Lds& lds = *reinterpret_cast<Lds*>(smem_raw);
+    Shared<kMaxK>& sh = lds;
     auto get = [&](int m, int64_t row) -> double {
         return row < rows ? R[row * ld + m] : __builtin_nan("");
     };
@@ -1233,6 +1408,17 @@ __global__ __launch_bounds__(kT) void weights_kernel(const double* R, int64_t ro
     else book_cov(sh, k, rows, get);
     const int tid = threadIdx.x;
     for (int e = tid; e < k * k; e += kT) cov[e] = sh.S[tri(e / k, e % k)];
+    if constexpr (MV) {
+        if (mu != nullptr) {
+            if (tid < k) {
+                const double v = mu[tid];
+                lds.gm[tid] = __builtin_isfinite(v) ? gamma * v : 0.0;
+            }
+            __syncthreads();
+        } else {
+            book_gm_history<kMaxK>(lds.gm, k, rows, gamma, get);
+        }
+    }
     bool capped = false;
     if (k * hi <= 1.0) {
         if (tid < k) sh.w[tid] = hi;
@@ -1241,9 +1427,9 @@ __global__ __launch_bounds__(kT) void weights_kernel(const double* R, int64_t ro
     } else if (k <= 32) {            // the solve rebalance_kernel<32> runs (headline books)
         const bool ok = qp_setup(sh, k);
         if (!ok) capped = true;
-        else if (tid < 64) capped = qp_wave(sh, k, lo, hi);
+        else if (tid < 64) capped = qp_wave<kMaxK, MV>(sh, k, lo, hi);
     } else {
-        capped = qp_block(sh, k, lo, hi, nullptr);
+        capped = qp_block<kMaxK, MV>(sh, k, lo, hi, nullptr);
     }
     __syncthreads();
     if (tid < k) w[tid] = sh.w[tid];
@@ -1252,11 +1438,16 @@ __global__ __launch_bounds__(kT) void weights_kernel(const double* R, int64_t ro
 
 // One workgroup per (rebalance date i = blockIdx.x, book side = blockIdx.y): side 0 the long
 // book (k largest predictions), side 1 the short book (k smallest).
-template <int KM>
+// MV: the mean-variance solve (afm_rebalance_mv_f64): the book's linear term gm = gamma * s * mu,
+// s = +1 / -1 for the long / short book, mu from the plane r.mu at the rebalance date (non-finite:
+// 0) or the members' means over the history window the covariance reads.
+template <int KM, bool MV = false>
 __global__ __launch_bounds__(kT) void rebalance_kernel(RebArgs r) {
     AFM_TAIL_PRIO_SET();
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    Shared<KM>& sh = *reinterpret_cast<Shared<KM>*>(smem_raw);
+    using Lds = typename std::conditional<MV, SharedMV<KM>, Shared<KM>>::type;
+    Lds& lds = *reinterpret_cast<Lds*>(smem_raw);
+    Shared<KM>& sh = lds;
     const int tid = threadIdx.x;
     const int64_t i = blockIdx.x;
     const int side = blockIdx.y;
@@ -1340,6 +1531,13 @@ __global__ __launch_bounds__(kT) void rebalance_kernel(RebArgs r) {
         const double hv = r.hist[tt * r.lda + a];
         return (th < hhi && ((wb >> (tt & 63)) & 1ull)) ? hv : __builtin_nan("");
     };
+    // MV, history source: the members' window means through the same accessor as the covariance
+    [[maybe_unused]] const double gs = side == 0 ? r.gamma : -r.gamma;
+    auto gm_history = [&](auto get) {
+        if constexpr (MV) {
+            if (r.mu == nullptr) book_gm_history<KM>(lds.gm, k, rows, gs, get);
+        }
+    };
     if (r.probe & 2) {
         for (int e = tid; e < k * (k + 1) / 2; e += kT) {
             int a = 0, q = e;
@@ -1361,6 +1559,7 @@ __global__ __launch_bounds__(kT) void rebalance_kernel(RebArgs r) {
             };
             if (k > 32) book_cov_mfma(sh, k, rows, fromT);
             else book_cov(sh, k, rows, fromT);
+            gm_history(fromT);
         }
     } else if (k * (k + 1) / 2 <= kT || r.hscr == nullptr) {
         if constexpr (KM == kMaxK) {
@@ -1369,6 +1568,7 @@ __global__ __launch_bounds__(kT) void rebalance_kernel(RebArgs r) {
         } else {
             book_cov(sh, k, rows, gather);
         }
+        gm_history(gather);
     } else {
         // several passes: gather the members' window once into a contiguous [member][row]
         // scratch block, which every pass then stages with coalesced reads
@@ -1401,6 +1601,16 @@ __global__ __launch_bounds__(kT) void rebalance_kernel(RebArgs r) {
         } else {
             book_cov(sh, k, rows, fromH);
         }
+        gm_history(fromH);
+    }
+    if constexpr (MV) {
+        if (r.mu != nullptr) {                       // plane source: one gather per member
+            if (tid < k) {
+                const double v = r.mu[t * r.lda + bk[tid]];
+                lds.gm[tid] = __builtin_isfinite(v) ? gs * v : 0.0;
+            }
+            __syncthreads();
+        }
     }
 
     // ---- exact box-constrained QP (primal active set, wave 0) -----------------------------
@@ -1414,13 +1624,13 @@ __global__ __launch_bounds__(kT) void rebalance_kernel(RebArgs r) {
         if (tid < k) sh.w[tid] = 1.0 / k;
     } else if (k > 0) {
         if constexpr (KM == kMaxK) {
-            capped = qp_block(sh, k, r.lo, r.hi,
-                              r.stamps ? r.stamps + (i * 2 + side) * 8 : nullptr);
+            capped = qp_block<KM, MV>(sh, k, r.lo, r.hi,
+                                      r.stamps ? r.stamps + (i * 2 + side) * 8 : nullptr);
         } else {
             const bool ok = qp_setup(sh, k);
             if (r.stamps && tid == 0) r.stamps[(i * 2 + side) * 8 + 6] = wall_clock64();
             if (!ok) capped = true;
-            else if (tid < 64) capped = qp_wave(sh, k, r.lo, r.hi);
+            else if (tid < 64) capped = qp_wave<KM, MV>(sh, k, r.lo, r.hi);
         }
     }
     if (capped && tid == 0) atomicOr(&r.status[i], 1);
@@ -1438,7 +1648,7 @@ __global__ __launch_bounds__(kT) void rebalance_kernel(RebArgs r) {
     }
     __syncthreads();
     if (tid == 0) {
-        r.sums[i * 4 + side] = pairwise_dense(sh.x, k);
+        r.sums[i * 4 + side] = pairwise_dense<MV>(sh.x, k);
         double den = 0.0;                                           // builtin sum(): 0 + ...
         for (int a = 0; a < k; ++a) den = den + sh.c[a];
         r.sums[i * 4 + 2 + side] = den;
@@ -2313,25 +2523,24 @@ static hipError_t launch_turnover_terms(afm_ctx* ctx, int64_t n, const int32_t* 
     return hipGetLastError();
 }
 
-template <int KM>
+template <int KM, bool MV = false>
 static int launch_rebalance(afm_ctx* ctx, const RebArgs& r) {
-    const size_t smem = sizeof(Shared<KM>);
-    AFM_HIP(afm_lds_opt_in(ctx, (const void*)rebalance_kernel<KM>, (int)smem));
-    hipLaunchKernelGGL(rebalance_kernel<KM>, dim3((unsigned)r.nd, 2), dim3(kT), smem, ctx->stream,
-                       r);
+    const size_t smem = MV ? sizeof(SharedMV<KM>) : sizeof(Shared<KM>);
+    AFM_HIP(afm_lds_opt_in(ctx, (const void*)rebalance_kernel<KM, MV>, (int)smem));
+    hipLaunchKernelGGL((rebalance_kernel<KM, MV>), dim3((unsigned)r.nd, 2), dim3(kT), smem,
+                       ctx->stream, r);
     AFM_HIP(hipGetLastError());
     return AFM_OK;
 }
 
-extern "C" int afm_rebalance_f64(afm_ctx* ctx, int64_t T, int64_t A, int64_t lda,
-                                 const int32_t* dates, int64_t nd, const double* pred,
-                                 const uint64_t* trad_bits, const double* hist,
-                                 const uint64_t* hist_bits, int64_t h_t0, int64_t h_t1,
-                                 int64_t window, const double* close, const double* tmr,
-                                 int top_n, double lo, double hi, int32_t* k_out,
-                                 int32_t* books, double* weights, double* sums, int32_t* upos,
-                                 int64_t* usize, int32_t* status) {
-    AFM_CTX(ctx);
+// afm_rebalance_f64 (mv false: mu and gamma unread) and afm_rebalance_mv_f64 (mv true)
+static int rebalance_run(afm_ctx* ctx, int64_t T, int64_t A, int64_t lda, const int32_t* dates,
+                         int64_t nd, const double* pred, const uint64_t* trad_bits,
+                         const double* hist, const uint64_t* hist_bits, int64_t h_t0,
+                         int64_t h_t1, int64_t window, const double* close, const double* tmr,
+                         int top_n, double lo, double hi, const bool mv, const double* mu,
+                         double gamma, int32_t* k_out, int32_t* books, double* weights,
+                         double* sums, int32_t* upos, int64_t* usize, int32_t* status) {
     AFM_CHECK_ARG(T > 0 && A > 0 && lda >= A && lda % 64 == 0, "bad panel shape");
     AFM_CHECK_ARG((A + 63) / 64 <= kMaxWords, "too many assets (max 32768)");
     AFM_CHECK_ARG(top_n >= 0 && top_n <= kMaxK, "top_n must be in [0, 128]");
@@ -2371,12 +2580,16 @@ extern "C" int afm_rebalance_f64(afm_ctx* ctx, int64_t T, int64_t A, int64_t lda
     }
     RebArgs r{T, lda, A, dates, nd, pred, trad_bits, hist, hist_bits, h_t0, h_t1, window, close,
               tmr, top_n, lo, hi, hscr, histT, hT0, hTn, hrows, 0, nullptr, k_out, books, weights,
-              sums, upos, usize, status};
+              sums, upos, usize, status, mu, gamma};
 #ifdef AFM_PROBE                     // profiling build (make prof): phase experiments
     if (const char* e = getenv("AFM_REB_PROBE")) r.probe = atoi(e);
+    if (mv) r.probe &= 4;            // the return term has no skip-phase experiments
 #endif
     if (r.probe & 4) AFM_HIP(hipMallocAsync((void**)&r.stamps, sizeof(int64_t) * nd * 16, ctx->stream));
-    const int rc = top_n <= 32 ? launch_rebalance<32>(ctx, r) : launch_rebalance<kMaxK>(ctx, r);
+    const int rc = mv ? (top_n <= 32 ? launch_rebalance<32, true>(ctx, r)
+                                     : launch_rebalance<kMaxK, true>(ctx, r))
+                      : (top_n <= 32 ? launch_rebalance<32>(ctx, r)
+                                     : launch_rebalance<kMaxK>(ctx, r));
     if (r.stamps) {                  // experiment: mean phase durations per workgroup
         std::vector<int64_t> h((size_t)nd * 16);
         AFM_HIP(hipMemcpyAsync(h.data(), r.stamps, sizeof(int64_t) * nd * 16, hipMemcpyDeviceToHost,
@@ -2397,6 +2610,37 @@ extern "C" int afm_rebalance_f64(afm_ctx* ctx, int64_t T, int64_t A, int64_t lda
         AFM_HIP(hipFree(r.stamps));
     }
     return rc;
+}
+
+extern "C" int afm_rebalance_f64(afm_ctx* ctx, int64_t T, int64_t A, int64_t lda,
+                                 const int32_t* dates, int64_t nd, const double* pred,
+                                 const uint64_t* trad_bits, const double* hist,
+                                 const uint64_t* hist_bits, int64_t h_t0, int64_t h_t1,
+                                 int64_t window, const double* close, const double* tmr,
+                                 int top_n, double lo, double hi, int32_t* k_out,
+                                 int32_t* books, double* weights, double* sums, int32_t* upos,
+                                 int64_t* usize, int32_t* status) {
+    AFM_CTX(ctx);
+    return rebalance_run(ctx, T, A, lda, dates, nd, pred, trad_bits, hist, hist_bits, h_t0, h_t1,
+                         window, close, tmr, top_n, lo, hi, false, nullptr, 0.0, k_out, books,
+                         weights, sums, upos, usize, status);
+}
+
+extern "C" int afm_rebalance_mv_f64(afm_ctx* ctx, int64_t T, int64_t A, int64_t lda,
+                                    const int32_t* dates, int64_t nd, const double* pred,
+                                    const uint64_t* trad_bits, const double* hist,
+                                    const uint64_t* hist_bits, int64_t h_t0, int64_t h_t1,
+                                    int64_t window, const double* close, const double* tmr,
+                                    int top_n, double lo, double hi, const double* mu,
+                                    double gamma, int32_t* k_out, int32_t* books,
+                                    double* weights, double* sums, int32_t* upos, int64_t* usize,
+                                    int32_t* status) {
+    AFM_CTX(ctx);
+    AFM_CHECK_ARG(gamma >= 0.0 && std::isfinite(gamma), "gamma must be finite and >= 0");
+    // gamma == 0 is the min-variance problem: the same kernels, bit for bit
+    return rebalance_run(ctx, T, A, lda, dates, nd, pred, trad_bits, hist, hist_bits, h_t0, h_t1,
+                         window, close, tmr, top_n, lo, hi, gamma > 0.0, mu, gamma, k_out, books,
+                         weights, sums, upos, usize, status);
 }
 
 extern "C" int afm_pnl_scan_f64(afm_ctx* ctx, int64_t nd, const int32_t* k_out,
@@ -2430,9 +2674,27 @@ extern "C" int afm_min_variance_weights_f64(afm_ctx* ctx, const double* R, int64
     AFM_CHECK_ARG(k >= 1 && k <= kMaxK && ld >= k && rows >= 0, "need 1 <= k <= 128, ld >= k");
     AFM_CHECK_ARG(R && w && cov && status && lo <= hi, "bad arguments");
     const size_t smem = sizeof(Shared<kMaxK>);
-    AFM_HIP(afm_lds_opt_in(ctx, (const void*)weights_kernel, (int)smem));
-    hipLaunchKernelGGL(weights_kernel, dim3(1), dim3(kT), smem, ctx->stream, R, rows, ld, k, lo,
-                       hi, w, cov, status);
+    AFM_HIP(afm_lds_opt_in(ctx, (const void*)weights_kernel<false>, (int)smem));
+    hipLaunchKernelGGL(weights_kernel<false>, dim3(1), dim3(kT), smem, ctx->stream, R, rows, ld, k,
+                       lo, hi, w, cov, status, (const double*)nullptr, 0.0);
+    AFM_HIP(hipGetLastError());
+    return AFM_OK;
+}
+
+extern "C" int afm_mean_variance_weights_f64(afm_ctx* ctx, const double* R, int64_t rows,
+                                             int64_t ld, int k, const double* mu, double gamma,
+                                             double lo, double hi, double* w, double* cov,
+                                             int32_t* status) {
+    AFM_CTX(ctx);
+    AFM_CHECK_ARG(gamma >= 0.0 && std::isfinite(gamma), "gamma must be finite and >= 0");
+    if (gamma == 0.0)                // the min-variance problem: the same kernel, bit for bit
+        return afm_min_variance_weights_f64(ctx, R, rows, ld, k, lo, hi, w, cov, status);
+    AFM_CHECK_ARG(k >= 1 && k <= kMaxK && ld >= k && rows >= 0, "need 1 <= k <= 128, ld >= k");
+    AFM_CHECK_ARG(R && w && cov && status && lo <= hi, "bad arguments");
+    const size_t smem = sizeof(SharedMV<kMaxK>);
+    AFM_HIP(afm_lds_opt_in(ctx, (const void*)weights_kernel<true>, (int)smem));
+    hipLaunchKernelGGL(weights_kernel<true>, dim3(1), dim3(kT), smem, ctx->stream, R, rows, ld, k,
+                       lo, hi, w, cov, status, mu, gamma);
     AFM_HIP(hipGetLastError());
     return AFM_OK;
 }

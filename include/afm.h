@@ -240,6 +240,7 @@ int afm_bootstrap_pnl_f64(afm_ctx* ctx, int64_t lda, const int32_t* dates, int64
  * -> pairwise-complete covariance cov[k][k] and the exact box-QP weights w[k]. */
 int afm_min_variance_weights_f64(afm_ctx* ctx, const double* R, int64_t rows, int64_t ld, int k,
                                  double lo, double hi, double* w, double* cov, int32_t* status);
+/* The rebalance and the one-book solve with an expected-return term: afm_mv.h. */
 
 /* ---- §8(f) rank 3: the talib factor variant (KKT:176-270) ------------------------------------
  * The 68 TA-Lib-defined columns for a calendar-grid panel (inputs as afm_factors_f64), out
