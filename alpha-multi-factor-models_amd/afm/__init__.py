@@ -9,6 +9,8 @@ Drop-in Python surface (same names, arguments and results as the reference):
 * ``Lasso(alpha, max_iter).fit/predict``           -- KKT:605-607 (coordinate descent)
 * ``lasso_path(X, y)`` / ``LassoCV(cv).fit``       -- scikit-learn's path and CV alpha selection
                                                     (the choice of alpha KKT:605 hard-codes)
+* ``FactorScreen(df, prices).run()``               -- KKT:465, 472 for every column at once
+                                                    (per-date IC, per-year IR, summary)
 * ``PortfolioManager(...)``                       -- KKT:795-970
 * ``split_zscore(all_df)``                       -- KKT:424-458 (z-score + split)
 
@@ -21,10 +23,11 @@ from . import regression  # noqa: F401
 from .regression import (Lasso, LassoCV, LinearRegression, cross_sectional_ols,  # noqa: F401
                          lasso_path)
 from .analyzer import AlphaSignalAnalyzer  # noqa: F401
+from .screen import FactorScreen, screen_grid  # noqa: F401
 from .portfolio import PortfolioManager, mean_variance_weights  # noqa: F401
 from .zscore import split_zscore, zscore_grid  # noqa: F401
 
 __all__ = ["compute_factors", "factor_panel", "FACTOR_NAMES", "PanelGrid", "pack_bits",
            "unpack_bits", "LinearRegression", "Lasso", "LassoCV", "lasso_path",
-           "cross_sectional_ols", "AlphaSignalAnalyzer",
+           "cross_sectional_ols", "AlphaSignalAnalyzer", "FactorScreen", "screen_grid",
            "PortfolioManager", "split_zscore", "zscore_grid"]

@@ -1,4 +1,5 @@
-"""ctypes binding of libafm.so (the C-ABI declared in include/afm.h and include/afm_mv.h).
+"""ctypes binding of libafm.so (the C-ABI declared in include/afm.h, include/afm_mv.h and
+include/afm_screen.h).
 
 The product path has no CPU fallback: if the library is missing or no GPU is visible, every
 call raises.  ``make -C alpha-multi-factor-models_amd`` (or ``__graft_entry__.build()``) builds
@@ -106,7 +107,13 @@ SIGNATURES_MV = {
     "afm_mean_variance_weights_f64": ("status", "ctx f64* i64 i64 int f64* f64 f64 f64 f64* f64* "
                                                 "i32*"),
 }
-TABLES = (SIGNATURES, SIGNATURES_MV)
+# ... and for include/afm_screen.h, the factor-screening entry points (tests/test_abi_screen.py)
+SIGNATURES_SCREEN = {
+    "afm_screen_ic_f64": ("status", "ctx f64* i64 i64 i64 i32* int f64* i32* i32* i64 f64* i32* "
+                                    "i32* f64*"),
+    "afm_screen_summary_f64": ("status", "ctx f64* i64 int i32* int int f64* f64* f64*"),
+}
+TABLES = (SIGNATURES, SIGNATURES_MV, SIGNATURES_SCREEN)
 _RESTYPE = {"status": I32, "int": I32, "i64": I64, "str": ctypes.c_char_p}
 _ARGTYPE = {"int": I32, "i64": I64, "f64": DBL, "str": ctypes.c_char_p}    # every pointer: void*
 
@@ -166,7 +173,7 @@ def _device_buffer(dtype, device: int, where: str):
 
 def _plans(device: int) -> dict:
     """name -> (takes the context, one converter per further parameter, failed(return value)):
-    how Context.call marshals each entry point of SIGNATURES and SIGNATURES_MV for the context of
+    how Context.call marshals each entry point of the signature tables for the context of
     ``device``."""
     import torch
     scalar = {"int": operator.index, "i64": operator.index, "f64": float}

@@ -235,6 +235,8 @@ class Pipeline:
         self._init_analyzer_buffers()
         self._init_streams()
         self._init_slabs()
+        self._stepped = False               # a step has filled the panel (factor_screen)
+        self._screen_bufs = None
 
     def _init_shard(self):
         """The asset shard: whole blocks of the fixed split, and this rank's slice of the grid."""
@@ -673,6 +675,7 @@ class Pipeline:
             self._stage_tail(mark)
         for s in self.streams:
             caller.wait_stream(s)
+        self._stepped = True
 
     def _stage_factors(self, mark):
         """factors + zstats: the panel, the row sets and the train window's z statistics; the
@@ -1027,6 +1030,66 @@ class Pipeline:
                 "mse_valid": score[:, 1].copy(), "r2_valid": score[:, 2].copy(),
                 "ic_valid": score[:, 3].copy(), "best": best, "alpha_": float(a[best]),
                 "beta": refit.cpu().numpy()}
+
+    def factor_screen(self, split: str = "train", z: bool = True, columns=None) -> dict:
+        """Factor screening on the last ``step()``'s resident panel (one GPU): the per-date
+        Pearson IC of every column against return_1 / 2 / 5, its per-year IR and whole-sample
+        summary (``afm.screen.screen_grid``) -- the reference's single-factor evaluation on a
+        split (KKT:465, 472), all columns in one pass, before anything is fitted.
+
+        ``split``: "train", "valid" or "test", the reference's inclusive date ranges (``Split``).
+        ``z=True``: the rows are the z-score rows of the split's dates and the values are z on the
+        fly from the train window's statistics (``df_train_x``); ``z=False``: the all_df rows and
+        the raw values.  The price rows are the all_df rows of the split's dates (``price_data =
+        df_train[['close_price']]``): forward returns do not look past the split.  ``columns``:
+        factor names (default: the pipeline's features; with ``z`` they must be features).
+
+        Runs on the caller's stream in buffers of its own (allocated on first use).  Returns host
+        arrays ``ic`` [nd][K][3], ``stats`` [K][3][5] (n, mean, std, IR, t), ``ir_year``
+        [nyears][K][3], ``nrows`` [T], ``dates_idx`` (calendar indices of the evaluated dates),
+        ``years``, ``year0`` and the names ``features``.  Pearson IC only: no rank IC, layers or
+        top-k per factor, and not the multi-GPU pipeline."""
+        import torch
+        from .screen import screen_grid
+        if self.W > 1:
+            raise NotImplementedError("factor_screen() runs on one GPU (world = 1)")
+        if not self._stepped:
+            raise ValueError("factor_screen(): run step() first (the panel is empty)")
+        sp, T, lda, nch, dev = self.sp, self.T, self.lda, self.nch, self.out.device
+        try:
+            t0, t1 = {"train": (0, sp.tr1), "valid": (sp.v0, sp.v1), "test": (sp.s0, T)}[split]
+        except KeyError:
+            raise ValueError(f"split={split!r}: expected train, valid or test") from None
+        names = list(columns) if columns is not None else list(self.features)
+        if z:
+            missing = [n for n in names if n not in self.features]
+            if missing:
+                raise ValueError(f"factor_screen(z=True): {missing} are not features of this "
+                                 "pipeline (no z statistics)")
+        cols = np.array([COL[n] for n in names], np.int32)
+        zcols = np.array([self.features.index(n) for n in names], np.int32) if z else None
+        if self._screen_bufs is None:
+            self._screen_bufs = {"row_bits": torch.zeros((nch, lda), **self._opts[1]),
+                                 "price_bits": torch.zeros((nch, lda), **self._opts[1])}
+        b = self._screen_bufs
+        a0 = (t0 // 64) * 64                # the split's sub-grid, 64-date aligned (bit words)
+        w0, w1 = a0 // 64, (t1 + 63) // 64
+        years = np.asarray(self.full.dates).astype("datetime64[Y]").astype(np.int64) + 1970
+        with self.ctx.on(torch.cuda.current_stream(dev)):                    # the caller's stream
+            call = self.ctx.call
+            call("afm_row_bits", nch, lda, self.zrows if z else self.alldf, None, None, t0, t1,
+                 b["row_bits"])
+            call("afm_row_bits", nch, lda, self.alldf, None, None, t0, t1, b["price_bits"])
+            r = screen_grid(self.out[0, a0:t1], cols, self.full.close[a0:t1],
+                            b["price_bits"][w0:w1], b["row_bits"][w0:w1], A=self.A,
+                            zs=self.zs if z else None, zcols=zcols, col_stride=T * lda,
+                            year=years[a0:t1], bufs=b)
+            out = {k: r[k].cpu().numpy() for k in ("ic", "stats", "ir_year")}
+            nrows = np.zeros(T, dtype=np.int32)
+            nrows[a0:t1] = r["nrows"].cpu().numpy()
+        out.update(nrows=nrows, dates_idx=r["dates_idx"] + np.int32(a0), years=r["years"],
+                   year0=r["year0"], features=names)
+        return out
 
     def summary(self) -> dict:
         """Host copies of the headline results (after a synchronize)."""

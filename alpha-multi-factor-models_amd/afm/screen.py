@@ -1,0 +1,192 @@
+"""Factor screening: the per-date IC of many factor columns in one pass.
+
+The reference evaluates single factors on the train split before it fits anything, one column at
+a time: ``AlphaSignalAnalyzer(df_train_x[['d11']], 'd11', df_train[['close_price']]).run()``
+("KKT Yuliang Jiang.py":465, 472).  All columns of one frame share the rows, the forward returns
+and the per-date demeans (KKT:308-320), so ``screen_grid`` prepares those once and evaluates the
+Pearson IC of every column per date (KKT:342-349), its per-year IR (KKT:351-354) and a
+whole-sample summary (csrc/screen.hip, include/afm_screen.h).  ``FactorScreen`` is the frame
+interface beside ``AlphaSignalAnalyzer``.
+
+Out of scope: rank (Spearman) IC -- ``corr_method`` stays Pearson, as in the reference -- the
+decile layers and the top-k backtest per factor, and the multi-GPU pipeline.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _lib
+from .analyzer import RETURN_TYPES, _dev
+from .grid import pack_bits, unpack_bits
+
+STATS = ["n", "mean", "std", "IR", "t"]
+
+
+def _buffer(bufs, name, shape, dtype, dev):
+    """A tensor of ``shape`` from the caller's buffer dict (allocated on first use, again when the
+    shape changes), or a fresh one."""
+    import torch
+    shape = tuple(int(s) for s in shape)
+    t = bufs.get(name) if bufs is not None else None
+    if t is None or tuple(t.shape) != shape or t.dtype is not dtype:
+        t = torch.empty(shape, dtype=dtype, device=dev)
+        if bufs is not None:
+            bufs[name] = t
+    return t
+
+
+def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zcols=None,
+                col_stride=None, dates_idx=None, year=None, bufs=None) -> dict:
+    """Device-level screen on grids.  ``base``: the panel, plane k of the screen at ``base +
+    cols[k] * col_stride`` ([T][lda] each; ``col_stride`` defaults to T * lda); ``close`` [T][lda]
+    with ``price_bits`` presence (the price rows of the forward returns); ``row_bits``: the row
+    set shared by every column.  ``zs`` (afm_zstats_finalize_f64's {mu, 1/sd} table): the values
+    are z = (x - mu) * (1/sd) of row ``zcols[k]`` (default row k), computed where they are read.
+    A non-finite value is skipped for its own column only (pandas nancorr).
+
+    One forward-return pass, one ``afm_xs_prepare_f64`` on a plane that is 0.0 on the rows and NaN
+    elsewhere (the shared merge / dropna cascade and demeans; A <= 32768 as there), then the IC
+    of every (date, column, return) and the summary.  ``dates_idx``: the evaluated dates (default:
+    those with rows); ``year`` [T]: calendar years for the per-year IR.  Pearson only; no layers
+    or top-k (use ``evaluate_grid`` on the columns that pass the screen).
+
+    Returns device tensors ``ic`` [nd][K][3], ``stats`` [K][3][5] (n, mean, std, IR, t over the
+    non-NaN ICs), ``ir_year`` [nyears][K][3], ``nrows``, ``rows_idx``, and the host arrays
+    ``dates_idx``, ``years``, ``year0``.  ``bufs``: a dict that keeps the work buffers between
+    calls."""
+    import torch
+    dev = close.device
+    T, lda = close.shape
+    f64, i32 = torch.float64, torch.int32
+    ctx = _lib.Context.get(dev.index)
+    ctx.bind_stream()
+    call = ctx.call
+
+    def dev_i32(v):
+        if isinstance(v, torch.Tensor):
+            return v.to(device=dev, dtype=i32).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(v, dtype=np.int32)).to(dev)
+
+    cols_t = dev_i32(cols)
+    K = int(cols_t.numel())
+    zc_t = dev_i32(zcols) if zcols is not None else None
+    if col_stride is None:
+        col_stride = T * lda
+    fr = _buffer(bufs, "fr", (3, T, lda), f64, dev)
+    call("afm_fwd_returns_f64", T, lda, close, price_bits, fr)
+    sig = _buffer(bufs, "sig", (T, lda), f64, dev)
+    sig.fill_(float("nan"))
+    sig.masked_fill_(unpack_bits(row_bits, T), 0.0)
+    scratch = _buffer(bufs, "scratch", (T, lda), f64, dev)
+    rows = _buffer(bufs, "rows", (4, T, lda), f64, dev)
+    rows_idx = _buffer(bufs, "rows_idx", (T, lda), i32, dev)
+    nrows = _buffer(bufs, "nrows", (T,), i32, dev)
+    call("afm_xs_prepare_f64", T, A, lda, sig, fr, scratch, rows, rows_idx, nrows)
+    if dates_idx is None:
+        dates_idx = np.flatnonzero(nrows.cpu().numpy() > 0)
+    dates_idx = np.ascontiguousarray(dates_idx, dtype=np.int32)
+    nd = len(dates_idx)
+    d_t = torch.from_numpy(dates_idx).to(dev)
+    ic = _buffer(bufs, "ic", (nd, K, 3), f64, dev)
+    call("afm_screen_ic_f64", base, col_stride, T, lda, cols_t, K, zs, zc_t, d_t, nd, rows,
+         rows_idx, nrows, ic)
+    if year is not None and nd:
+        yr = np.ascontiguousarray(np.asarray(year)[dates_idx], dtype=np.int32)
+        y0, ny = int(yr.min()), int(yr.max() - yr.min() + 1)
+    else:
+        yr, y0, ny = np.zeros(nd, dtype=np.int32), 0, 0
+    y_t = torch.from_numpy(yr).to(dev) if nd else torch.zeros(1, dtype=i32, device=dev)
+    stats = _buffer(bufs, "stats", (K, 3, 5), f64, dev)
+    ir_year = _buffer(bufs, "ir_year", (ny, K, 3), f64, dev)
+    sscr = _buffer(bufs, "summary_scratch", (K, 3, 2, max(nd, 1)), f64, dev)
+    call("afm_screen_summary_f64", ic if nd else sscr, nd, K, y_t, ny, y0, stats,
+         ir_year if ny else sscr, sscr)
+    return {"ic": ic, "stats": stats, "ir_year": ir_year, "nrows": nrows, "rows_idx": rows_idx,
+            "dates_idx": dates_idx, "years": yr, "year0": y0}
+
+
+class FactorScreen:
+    """``FactorScreen(factors_df, price_data, columns=None).run()``: the IC / IR screen of every
+    column of ``factors_df`` -- indexed (date, id), one column per factor, e.g. the reference's
+    ``df_train_x`` -- against the forward returns of ``price_data`` (what ``AlphaSignalAnalyzer``
+    takes: indexed (date, id), a ``close_price`` column).  The row set is the frame's rows; a NaN
+    or inf cell is skipped for its own column only.  For a column without NaN the results are
+    those of ``AlphaSignalAnalyzer(factors_df[[c]], c, price_data)``'s ``ic_df`` / ``ir_df``.
+
+    After ``run()``: ``ic_df`` (date, factor, Type, IC; NaN ICs dropped; ordered by date, factor
+    in column order, Type), ``ir_df`` (year, factor, Type, IR) and ``summary`` (factor, Type, n,
+    mean, std, IR, t; by \\|IR\\| descending, ties in column order, NaN last).  Pearson IC only;
+    layers and the top-k backtest are the analyzer's."""
+
+    def __init__(self, factors_df, price_data, columns=None):
+        self.factors_df = factors_df
+        self.columns = list(columns) if columns is not None else list(factors_df.columns)
+        self.return_type = list(RETURN_TYPES)
+        self.price_data = price_data
+        self._res = None
+
+    def run(self):
+        import pandas as pd
+        import torch
+        fd = self.factors_df.reset_index()
+        pdat = self.price_data.reset_index()
+        dcol, icol = fd.columns[0], fd.columns[1]
+        sd = fd[dcol].to_numpy().astype("datetime64[ns]")
+        si = fd[icol].to_numpy().astype(np.int64)
+        pd_ = pdat[pdat.columns[0]].to_numpy().astype("datetime64[ns]")
+        pi_ = pdat[pdat.columns[1]].to_numpy().astype(np.int64)
+        pc = pdat["close_price"].to_numpy(np.float64)
+        dates = np.unique(np.concatenate([sd, pd_]))
+        ids = np.unique(np.concatenate([si, pi_]))
+        T, A, K = len(dates), len(ids), len(self.columns)
+        lda = (A + 63) // 64 * 64
+        dev = _dev()
+        st = torch.from_numpy(np.searchsorted(dates, sd)).to(dev)
+        sa = torch.from_numpy(np.searchsorted(ids, si)).to(dev)
+        base = torch.full((K, T, lda), float("nan"), dtype=torch.float64, device=dev)
+        vals = np.ascontiguousarray(fd[self.columns].to_numpy(np.float64).T)
+        base[:, st, sa] = torch.from_numpy(vals).to(dev)
+        rm = torch.zeros((T, lda), dtype=torch.bool, device=dev)
+        rm[st, sa] = True
+        pt = torch.from_numpy(np.searchsorted(dates, pd_)).to(dev)
+        pa = torch.from_numpy(np.searchsorted(ids, pi_)).to(dev)
+        close = torch.full((T, lda), float("nan"), dtype=torch.float64, device=dev)
+        close[pt, pa] = torch.from_numpy(np.ascontiguousarray(pc)).to(dev)
+        pm = torch.zeros((T, lda), dtype=torch.bool, device=dev)
+        pm[pt, pa] = True
+        year = dates.astype("datetime64[Y]").astype(np.int64) + 1970
+        r = screen_grid(base, np.arange(K), close, pack_bits(pm), pack_bits(rm), A=A, year=year)
+        r["dates"], r["ids"] = dates, ids
+        self._res = r
+        ic = r["ic"].cpu().numpy()                                   # [nd][K][3]
+        nd = ic.shape[0]
+        dts = pd.DatetimeIndex(dates[r["dates_idx"]])
+        names = np.asarray(self.columns, dtype=object)
+        types = np.asarray(self.return_type, dtype=object)
+        keep = ~np.isnan(ic.reshape(-1))
+        self.ic_df = pd.DataFrame({
+            "date": np.repeat(dts.values, K * 3)[keep],
+            "factor": np.tile(np.repeat(names, 3), nd)[keep],
+            "Type": np.tile(types, nd * K)[keep],
+            "IC": ic.reshape(-1)[keep]})
+        ir = r["ir_year"].cpu().numpy()                              # [ny][K][3]
+        ny = ir.shape[0]
+        # a (year, factor, Type) row exists where the year has an IC (the reference's groupby)
+        has = np.zeros((max(ny, 1), K, 3), dtype=bool)
+        if nd:
+            np.logical_or.at(has, r["years"] - r["year0"], ~np.isnan(ic))
+        has = has[:ny].reshape(-1)
+        self.ir_df = pd.DataFrame({
+            "year": np.repeat(np.arange(ny, dtype=np.int64) + r["year0"], K * 3)[has],
+            "factor": np.tile(np.repeat(names, 3), ny)[has],
+            "Type": np.tile(types, ny * K)[has],
+            "IR": ir.reshape(-1)[has]})
+        st_ = r["stats"].cpu().numpy().reshape(K * 3, 5)
+        key = np.abs(st_[:, 3])
+        order = np.argsort(np.where(np.isnan(key), -np.inf, key) * -1.0, kind="stable")
+        summary = pd.DataFrame(st_, columns=STATS)
+        summary["n"] = summary["n"].astype(np.int64)
+        summary.insert(0, "Type", np.tile(types, K))
+        summary.insert(0, "factor", np.repeat(names, 3))
+        self.summary = summary.iloc[order].reset_index(drop=True)
+        return self

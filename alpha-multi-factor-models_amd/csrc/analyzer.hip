@@ -25,6 +25,8 @@
 
 #pragma clang fp contract(off)
 
+#include "afm_np_sum.h"                // qnan, leaf_sum, kNpBuf, seq_pairwise, seq_np_sum
+
 namespace afm {
 namespace {
 
@@ -36,7 +38,6 @@ constexpr int kMaxLeaves = 1024;      // pairwise leaves (n <= 65536)
 constexpr int kTopK = 10;
 constexpr int kLayers = 10;
 
-__device__ __forceinline__ double qnan() { return __builtin_nan(""); }
 __device__ __forceinline__ bool bit_at(const uint64_t* bits, int64_t lda, int64_t t, int64_t a) {
     return (bits[(t >> 6) * lda + a] >> (t & 63)) & 1ull;
 }
@@ -137,27 +138,8 @@ __device__ double pw_combine(PwShared& p, int64_t n) {
     return a + b;
 }
 
-__device__ double leaf_sum(const double* a, int n) {
-    if (n < 8) {
-        double res = 0.;
-        for (int i = 0; i < n; ++i) res += a[i];
-        return res;
-    }
-    double r[8];
-    for (int j = 0; j < 8; ++j) r[j] = a[j];
-    int i;
-    for (i = 8; i < n - (n % 8); i += 8)
-        for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res += a[i];
-    return res;
-}
-
-// np.add.reduce of v[0..n) -- the identity 0.0, then numpy's pairwise sums of the consecutive
-// kNpBuf-element buffers of the ufunc's buffered reduction added one by one (over 8192 elements
-// the sum is not one pairwise tree: oracle np_sum, pinned to numpy in tests/test_oracle_golden.py)
-// -- evaluated by the whole block
-constexpr int64_t kNpBuf = 8192;
+// np.add.reduce of v[0..n) (afm_np_sum.h: numpy's pairwise sums of the consecutive kNpBuf-element
+// buffers added one by one onto 0.0) evaluated by the whole block
 template <int NT = kT>
 __device__ double block_np_sum(PwShared& p, const double* v, int64_t n) {
     const int tid = threadIdx.x;
@@ -927,18 +909,6 @@ __global__ __launch_bounds__(128) void xs_stats_kernel(StatArgs g) {
 }
 
 // ---- series: cumulative layers / long-short / top-k, per-year IR -----------------------------
-__device__ double seq_pairwise(const double* a, int64_t n) {   // numpy pairwise_sum, one thread
-    if (n <= 128) return leaf_sum(a, (int)n);
-    int64_t n2 = n / 2;
-    n2 -= n2 % 8;
-    return seq_pairwise(a, n2) + seq_pairwise(a + n2, n - n2);
-}
-__device__ double seq_np_sum(const double* a, int64_t n) {      // np.add.reduce (block_np_sum)
-    double r = 0.0;
-    for (int64_t c0 = 0; c0 < n; c0 += kNpBuf) r = r + seq_pairwise(a + c0, n - c0 < kNpBuf ? n - c0 : kNpBuf);
-    return r;
-}
-
 // One workgroup.  Every series is a sequential recurrence over the dates, so each runs in one
 // lane; its inputs are read in batches of kSerB (all issued before the batch's dependent sums and
 // stores), and the per-year IC samples of the IR sit in LDS (up to 366 of a year; a year with

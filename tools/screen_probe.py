@@ -1,0 +1,196 @@
+"""Time the factor screen at the bench workload's train split (config C: 10,000 assets x 5,040
+days; the 97 z-scored feature columns on the z-score rows of the train dates, pipeline state after
+one step): the shared preparation, screen_ic_kernel alone, the summary alone, and -- for comparison
+-- the loop the screen replaces, ``evaluate_grid`` once per column (8 calls, scaled to 97).
+    python tools/screen_probe.py                 every step, each in a child process with its own
+                                                 time limit; stops at the first failure
+    python tools/screen_probe.py --step ic       one step in this process
+One GPU; reads nothing outside the repository."""
+import argparse
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "alpha-multi-factor-models_amd")]
+
+STEPS = {"prep": 420, "ic": 420, "summary": 420, "loop": 600}      # time limit, seconds
+HBM_TBS = 8.0                                                       # MI355X peak
+
+
+def median_ms(fn, reps=5):
+    import numpy as np
+    import torch
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    fn()
+    ts = []
+    for _ in range(reps):
+        ev[0].record()
+        fn()
+        ev[1].record()
+        torch.cuda.synchronize()
+        ts.append(ev[0].elapsed_time(ev[1]))
+    return float(np.median(ts))
+
+
+def state(assets, days):
+    """The stepped pipeline and the train split's screen inputs (sub-grid [0, tr1))."""
+    import numpy as np
+    import torch
+    import afm
+    from afm.pipeline import Pipeline
+    from afm.synthetic import make_panel
+    pipe = Pipeline(afm.PanelGrid.from_panel(make_panel(assets, days, seed=2023, tradable_p=0.9)))
+    pipe.step()
+    torch.cuda.synchronize()
+    T, lda, nch, t1 = pipe.T, pipe.lda, pipe.nch, pipe.sp.tr1
+    call = pipe.ctx.call
+    pipe.ctx.bind_stream()
+    rb, pb = torch.zeros_like(pipe.zrows), torch.zeros_like(pipe.alldf)
+    call("afm_row_bits", nch, lda, pipe.zrows, None, None, 0, t1, rb)
+    call("afm_row_bits", nch, lda, pipe.alldf, None, None, 0, t1, pb)
+    w1 = (t1 + 63) // 64
+    years = np.asarray(pipe.full.dates).astype("datetime64[Y]").astype(np.int64) + 1970
+    return dict(pipe=pipe, call=call, T=t1, lda=lda, A=pipe.A, stride=T * lda, rb=rb[:w1],
+                pb=pb[:w1], close=pipe.full.close[:t1], base=pipe.out[0, :t1], year=years[:t1])
+
+
+def prepared(s):
+    """The shared preparation, one launch at a time -> buffers and the timed closures."""
+    import torch
+    from afm.grid import unpack_bits
+    T, lda, dev, call = s["T"], s["lda"], s["close"].device, s["call"]
+    f64 = dict(dtype=torch.float64, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    b = dict(fr=torch.empty((3, T, lda), **f64), sig=torch.empty((T, lda), **f64),
+             scratch=torch.empty((T, lda), **f64), rows=torch.empty((4, T, lda), **f64),
+             rows_idx=torch.empty((T, lda), **i32), nrows=torch.empty(T, **i32))
+
+    def rowplane():
+        b["sig"].fill_(float("nan"))
+        b["sig"].masked_fill_(unpack_bits(s["rb"], T), 0.0)
+    fns = {"fwd_returns": lambda: call("afm_fwd_returns_f64", T, lda, s["close"], s["pb"], b["fr"]),
+           "row_plane": rowplane,
+           "xs_prepare": lambda: call("afm_xs_prepare_f64", T, s["A"], lda, b["sig"], b["fr"],
+                                      b["scratch"], b["rows"], b["rows_idx"], b["nrows"])}
+    return b, fns
+
+
+def screen_buffers(s, b):
+    import numpy as np
+    import torch
+    pipe, dev = s["pipe"], s["close"].device
+    nr = b["nrows"].cpu().numpy()
+    didx = np.flatnonzero(nr > 0).astype(np.int32)
+    yr = s["year"][didx].astype(np.int32)
+    K, nd = pipe.p, len(didx)
+    return dict(K=K, nd=nd, nr=nr, didx=didx, d_t=torch.from_numpy(didx).to(dev),
+                y_t=torch.from_numpy(yr).to(dev), y0=int(yr.min()),
+                ny=int(yr.max() - yr.min() + 1),
+                ic=torch.empty((nd, K, 3), dtype=torch.float64, device=dev))
+
+
+def run_step(step, assets, days):
+    import numpy as np
+    import torch
+    s = state(assets, days)
+    pipe, call, T, lda = s["pipe"], s["call"], s["T"], s["lda"]
+    b, fns = prepared(s)
+    print(f"[{step}] train split: {T} dates x {lda} (A = {s['A']}), K = {pipe.p} columns", flush=True)
+    if step == "prep":
+        total = 0.0
+        for name, fn in fns.items():
+            ms = median_ms(fn)
+            total += ms
+            print(f"prep {name}: {ms:.3f} ms", flush=True)
+        print(f"prep total: {total:.3f} ms; rows per date mean "
+              f"{b['nrows'].float().mean().item():.0f}", flush=True)
+        return
+    for fn in fns.values():
+        fn()
+    q = screen_buffers(s, b)
+    K, nd = q["K"], q["nd"]
+    cells = int(q["nr"][q["didx"]].sum())
+
+    def ic():
+        call("afm_screen_ic_f64", s["base"], s["stride"], T, lda, pipe.feat, K, pipe.zs, None,
+             q["d_t"], nd, b["rows"], b["rows_idx"], b["nrows"], q["ic"])
+    if step == "ic":
+        ms = median_ms(ic)
+        panel = cells * K * 8
+        ngrp = (K + 63) // 64
+        other = cells * ngrp * (3 * 8 + 4) + cells * K * 16          # returns + idx; zs (cached)
+        print(f"screen_ic: {ms:.3f} ms for {nd} dates, {cells} rows, K = {K}", flush=True)
+        print(f"screen_ic panel bytes {panel / 1e9:.2f} GB -> {panel / ms / 1e9:.3f} TB/s "
+              f"({panel / ms / 1e9 / HBM_TBS:.1%} of {HBM_TBS} TB/s HBM); with the z table "
+              f"(L2 / MALL resident), returns and indices {(panel + other) / 1e9:.2f} GB "
+              f"requested", flush=True)
+        steps = cells * ngrp                     # one wave-step per (row, 64-column group)
+        print(f"screen_ic chain: {steps} wave row-steps, {ms * 1e6 / steps * 256 * 4:.1f} ns "
+              f"of one SIMD per row-step if all {256 * 4} SIMDs are busy", flush=True)
+        raw = torch.empty_like(q["ic"])
+        ms_raw = median_ms(lambda: call("afm_screen_ic_f64", s["base"], s["stride"], T, lda,
+                                        pipe.feat, K, None, None, q["d_t"], nd, b["rows"],
+                                        b["rows_idx"], b["nrows"], raw))
+        print(f"screen_ic raw values (no z table): {ms_raw:.3f} ms -> "
+              f"{panel / ms_raw / 1e9:.3f} TB/s", flush=True)
+        return
+    ic()
+    if step == "summary":
+        stats = torch.empty((K, 3, 5), dtype=torch.float64, device=q["ic"].device)
+        iry = torch.empty((q["ny"], K, 3), dtype=torch.float64, device=q["ic"].device)
+        scr = torch.empty((K, 3, 2, nd), dtype=torch.float64, device=q["ic"].device)
+        ms = median_ms(lambda: call("afm_screen_summary_f64", q["ic"], nd, K, q["y_t"], q["ny"],
+                                    q["y0"], stats, iry, scr))
+        print(f"screen_summary: {ms:.3f} ms for {nd} dates, {q['ny']} years, K = {K}", flush=True)
+        return
+    assert step == "loop"
+    # the loop the screen replaces: evaluate_grid per column (its sig plane built with torch --
+    # the only way to screen without the new entry points); 8 columns, scaled to K
+    from afm.analyzer import evaluate_grid
+    from afm.grid import unpack_bits
+    rowm = unpack_bits(s["rb"], T)
+    nan = torch.full((T, lda), float("nan"), dtype=torch.float64, device=rowm.device)
+    ncall, t_sig, t_eval, same = 8, [], [], True
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+    for k in range(ncall):
+        c = int(pipe.feat[k].item())
+        ev[0].record()
+        z = (pipe.out[c, :T] - pipe.zs[k, :, 0]) * pipe.zs[k, :, 1]
+        sig = torch.where(rowm, z, nan)
+        ev[1].record()
+        one = evaluate_grid(sig, s["close"], s["pb"], A=s["A"], dates_idx=q["didx"],
+                            year=s["year"])
+        ev[2].record()
+        torch.cuda.synchronize()
+        t_sig.append(ev[0].elapsed_time(ev[1]))
+        t_eval.append(ev[1].elapsed_time(ev[2]))
+        a, g = one["ic"].cpu().numpy(), q["ic"][:, k, :].cpu().numpy()
+        same = same and bool(((a == g) | (np.isnan(a) & np.isnan(g))).all())
+    per = float(np.median(t_eval))
+    print(f"loop evaluate_grid: {per:.3f} ms per column (median of {ncall}; sig plane "
+          f"{float(np.median(t_sig)):.3f} ms more) -> {per * K:.1f} ms for K = {K} columns, "
+          f"{ncall} calls scaled", flush=True)
+    print(f"loop ic of the {ncall} columns bit-equal to the screen's: {same}", flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--step", choices=sorted(STEPS))
+    ap.add_argument("--assets", type=int, default=10000)
+    ap.add_argument("--days", type=int, default=5040)
+    a = ap.parse_args()
+    if a.step:
+        return run_step(a.step, a.assets, a.days)
+    for step, limit in STEPS.items():
+        cmd = ["timeout", "-k", "10", str(limit), sys.executable, "-u", os.path.abspath(__file__),
+               "--step", step, "--assets", str(a.assets), "--days", str(a.days)]
+        rc = subprocess.run(cmd).returncode
+        if rc != 0:
+            print(f"step {step} ended with status {rc}: stopping", flush=True)
+            return rc
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
