@@ -1,5 +1,5 @@
-"""ctypes binding of libafm.so (the C-ABI declared in include/afm.h, include/afm_mv.h and
-include/afm_screen.h).
+"""ctypes binding of libafm.so (the C-ABI declared in include/afm.h, include/afm_mv.h,
+include/afm_screen.h and include/afm_rankic.h).
 
 The product path has no CPU fallback: if the library is missing or no GPU is visible, every
 call raises.  ``make -C alpha-multi-factor-models_amd`` (or ``__graft_entry__.build()``) builds
@@ -114,6 +114,14 @@ SIGNATURES_SCREEN = {
     "afm_screen_summary_f64": ("status", "ctx f64* i64 int i32* int int f64* f64* f64*"),
 }
 TABLES = (SIGNATURES, SIGNATURES_MV, SIGNATURES_SCREEN)
+# ... and for include/afm_rankic.h, the rank (Spearman) IC entry points (tests/test_abi_rankic.py)
+SIGNATURES_RANK = {
+    "afm_rank_scratch_words": ("i64", "i64"),
+    "afm_rank_returns_f64": ("status", "ctx i64 i64 i32* i64 f64* i32* i32* i64* i64*"),
+    "afm_screen_rank_ic_f64": ("status", "ctx f64* i64 i64 i64 i32* int f64* i32* i32* i64 f64* "
+                                         "i32* i32* i32* i64* i64* f64*"),
+}
+ALL_TABLES = TABLES + (SIGNATURES_RANK,)       # what lib() declares and Context.call resolves
 _RESTYPE = {"status": I32, "int": I32, "i64": I64, "str": ctypes.c_char_p}
 _ARGTYPE = {"int": I32, "i64": I64, "f64": DBL, "str": ctypes.c_char_p}    # every pointer: void*
 
@@ -135,7 +143,7 @@ def lib():
                     raise ImportError(f"{LIB_PATH} is not built: run `make -C "
                                       f"{os.path.dirname(HERE)}` (hipcc, gfx950)")
                 L = ctypes.CDLL(LIB_PATH)
-                for table in TABLES:
+                for table in ALL_TABLES:
                     for name, (res, params) in table.items():
                         f = getattr(L, name)
                         f.restype = _RESTYPE[res]
@@ -181,7 +189,7 @@ def _plans(device: int) -> dict:
     negative = (0).__gt__
     failed = {"status": bool, "int": negative, "i64": negative, "str": lambda s: s is None}
     plans = {}
-    for name, (res, params) in (item for table in TABLES for item in table.items()):
+    for name, (res, params) in (item for table in ALL_TABLES for item in table.items()):
         toks = params.split()
         takes_ctx = toks[:1] == ["ctx"]
         convs = tuple(_device_buffer(buffer[t], device, f"{name} argument {i}") if t in buffer

@@ -5,6 +5,8 @@ SURVEY.md §8(a) rows A1-A4.
 top-10 backtest on the GPU (csrc/analyzer.hip) and rebuilds the reference's attributes
 (``factor_df``, ``ic_df``, ``ir_df``, ``layered_ret_dfs``, ``ls_ret_dfs``, ``port_ret_df``,
 ``port_df``) with the same columns, row order and values (bit-exact with pandas 2.3.3).
+``corr_method`` is read at run time as in the reference (KKT:286, 344-345): 'pearson' (default) or
+'spearman', the rank IC (csrc/rankic.hip); ``ic_df`` and ``ir_df`` follow it.
 Plotting (``_gen_report``, KKT:377-419) is out of scope and does nothing.  ``ic_df`` carries a
 fresh RangeIndex (the reference's keeps the gaps of its dropped 'id' rows).
 """
@@ -23,10 +25,56 @@ def _dev():
     return torch.device("cuda", torch.cuda.current_device())
 
 
-def evaluate_grid(sig, close, price_bits, *, A: int, dates_idx=None, year=None):
-    """Device-level A1-A4 on grids: ``sig`` [T][lda] (NaN = no row), ``close`` [T][lda] with
-    ``price_bits`` presence.  Returns a dict of device tensors."""
+def check_corr_method(method) -> str:
+    """The reference's ``corr_method`` (what ``DataFrame.corr`` takes): 'pearson' or 'spearman'."""
+    if method == "kendall":
+        raise NotImplementedError("corr_method='kendall' is not implemented (pearson, spearman)")
+    if method not in ("pearson", "spearman"):
+        raise ValueError(f"corr_method={method!r}: expected 'pearson' or 'spearman'")
+    return method
+
+
+def _buffer(bufs, name, shape, dtype, dev):
+    """A tensor of ``shape`` from the caller's buffer dict (allocated on first use, again when the
+    shape changes), or a fresh one."""
     import torch
+    shape = tuple(int(s) for s in shape)
+    t = bufs.get(name) if bufs is not None else None
+    if t is None or tuple(t.shape) != shape or t.dtype is not dtype:
+        t = torch.empty(shape, dtype=dtype, device=dev)
+        if bufs is not None:
+            bufs[name] = t
+    return t
+
+
+def rank_ic(call, base, col_stride, cols_t, K, zs, zc_t, d_t, nd, rows, rows_idx, nrows, ic,
+            bufs=None):
+    """The Spearman IC of K columns on prepared rows into ``ic`` [nd][K][3]: the return ranks of
+    the evaluated dates once (afm_rank_returns_f64), then every (date, column)
+    (afm_screen_rank_ic_f64).  Arguments as afm_screen_ic_f64's; work buffers in ``bufs``."""
+    import torch
+    if nd == 0:
+        return ic
+    T, lda = rows_idx.shape
+    dev = rows.device
+    words = call("afm_rank_scratch_words", lda)
+    scr = _buffer(bufs, "rank_scratch", (max(words, 1),), torch.int64, dev)
+    rrank = _buffer(bufs, "rrank", (3, T, lda), torch.int32, dev)
+    rsum = _buffer(bufs, "rsum", (T, 3), torch.int64, dev)
+    call("afm_rank_returns_f64", T, lda, d_t, nd, rows, nrows, rrank, rsum, scr)
+    call("afm_screen_rank_ic_f64", base, col_stride, T, lda, cols_t, K, zs, zc_t, d_t, nd, rows,
+         rows_idx, nrows, rrank, rsum, scr, ic)
+    return ic
+
+
+def evaluate_grid(sig, close, price_bits, *, A: int, dates_idx=None, year=None,
+                  corr_method="pearson"):
+    """Device-level A1-A4 on grids: ``sig`` [T][lda] (NaN = no row), ``close`` [T][lda] with
+    ``price_bits`` presence.  Returns a dict of device tensors.  ``corr_method='spearman'``:
+    ``ic`` (and the ``ir`` computed from it) is the rank IC, the Pearson IC is kept as
+    ``ic_pearson``; every other key is unchanged."""
+    import torch
+    check_corr_method(corr_method)
     dev = sig.device
     T, lda = sig.shape
     plane = T * lda
@@ -59,6 +107,12 @@ def evaluate_grid(sig, close, price_bits, *, A: int, dates_idx=None, year=None):
     out = {"fr": fr, "rows": rows, "rows_idx": rows_idx, "nrows": nrows, "rank_asc": ra,
            "rank_desc": rd, "dates_idx": dates_idx, "ic": ic, "layer_mean": lm,
            "layer_cnt": lc, "port": port, "mcols": mcols}
+    if corr_method == "spearman":
+        out["ic_pearson"] = ic
+        ic = torch.empty((nd, 1, 3), dtype=torch.float64, device=dev)
+        cols_t = torch.zeros(1, dtype=torch.int32, device=dev)
+        rank_ic(call, sig, 0, cols_t, 1, None, None, d_t, nd, rows, rows_idx, nrows, ic)
+        out["ic"] = ic = ic.view(nd, 3)
     if year is not None and nd:
         yr = np.asarray(year, dtype=np.int32)[dates_idx]
         y0, ny = int(yr.min()), int(yr.max() - yr.min() + 1)
@@ -129,7 +183,8 @@ class AlphaSignalAnalyzer:
         pm = torch.zeros((T, lda), dtype=torch.bool, device=dev)
         pm[ti, ai] = True
         year = dates.astype("datetime64[Y]").astype(np.int64) + 1970
-        res = evaluate_grid(sig, close, pack_bits(pm), A=A, year=year)
+        res = evaluate_grid(sig, close, pack_bits(pm), A=A, year=year,
+                            corr_method=self.corr_method)
         res["dates"], res["ids"] = dates, ids
         self._res = res
 

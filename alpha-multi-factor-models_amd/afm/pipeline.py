@@ -1031,9 +1031,11 @@ class Pipeline:
                 "ic_valid": score[:, 3].copy(), "best": best, "alpha_": float(a[best]),
                 "beta": refit.cpu().numpy()}
 
-    def factor_screen(self, split: str = "train", z: bool = True, columns=None) -> dict:
-        """Factor screening on the last ``step()``'s resident panel (one GPU): the per-date
-        Pearson IC of every column against return_1 / 2 / 5, its per-year IR and whole-sample
+    def factor_screen(self, split: str = "train", z: bool = True, columns=None,
+                      corr_method: str = "pearson") -> dict:
+        """Factor screening on the last ``step()``'s resident panel (one GPU): the per-date IC
+        (``corr_method``: 'pearson', or 'spearman' for the rank IC) of every column against
+        return_1 / 2 / 5, its per-year IR and whole-sample
         summary (``afm.screen.screen_grid``) -- the reference's single-factor evaluation on a
         split (KKT:465, 472), all columns in one pass, before anything is fitted.
 
@@ -1047,10 +1049,12 @@ class Pipeline:
         Runs on the caller's stream in buffers of its own (allocated on first use).  Returns host
         arrays ``ic`` [nd][K][3], ``stats`` [K][3][5] (n, mean, std, IR, t), ``ir_year``
         [nyears][K][3], ``nrows`` [T], ``dates_idx`` (calendar indices of the evaluated dates),
-        ``years``, ``year0`` and the names ``features``.  Pearson IC only: no rank IC, layers or
-        top-k per factor, and not the multi-GPU pipeline."""
+        ``years``, ``year0`` and the names ``features``.  No layers or top-k per factor, and not
+        the multi-GPU pipeline."""
         import torch
+        from .analyzer import check_corr_method
         from .screen import screen_grid
+        check_corr_method(corr_method)
         if self.W > 1:
             raise NotImplementedError("factor_screen() runs on one GPU (world = 1)")
         if not self._stepped:
@@ -1083,7 +1087,7 @@ class Pipeline:
             r = screen_grid(self.out[0, a0:t1], cols, self.full.close[a0:t1],
                             b["price_bits"][w0:w1], b["row_bits"][w0:w1], A=self.A,
                             zs=self.zs if z else None, zcols=zcols, col_stride=T * lda,
-                            year=years[a0:t1], bufs=b)
+                            year=years[a0:t1], bufs=b, corr_method=corr_method)
             out = {k: r[k].cpu().numpy() for k in ("ic", "stats", "ir_year")}
             nrows = np.zeros(T, dtype=np.int32)
             nrows[a0:t1] = r["nrows"].cpu().numpy()

@@ -4,39 +4,27 @@ The reference evaluates single factors on the train split before it fits anythin
 a time: ``AlphaSignalAnalyzer(df_train_x[['d11']], 'd11', df_train[['close_price']]).run()``
 ("KKT Yuliang Jiang.py":465, 472).  All columns of one frame share the rows, the forward returns
 and the per-date demeans (KKT:308-320), so ``screen_grid`` prepares those once and evaluates the
-Pearson IC of every column per date (KKT:342-349), its per-year IR (KKT:351-354) and a
-whole-sample summary (csrc/screen.hip, include/afm_screen.h).  ``FactorScreen`` is the frame
-interface beside ``AlphaSignalAnalyzer``.
+IC of every column per date (KKT:342-349) -- Pearson, or with ``corr_method='spearman'`` the rank
+IC (the reference's ``corr_method`` attribute, KKT:286) -- its per-year IR (KKT:351-354) and a
+whole-sample summary (csrc/screen.hip, csrc/rankic.hip, include/afm_screen.h,
+include/afm_rankic.h).  ``FactorScreen`` is the frame interface beside ``AlphaSignalAnalyzer``.
 
-Out of scope: rank (Spearman) IC -- ``corr_method`` stays Pearson, as in the reference -- the
-decile layers and the top-k backtest per factor, and the multi-GPU pipeline.
+Out of scope: the decile layers and the top-k backtest per factor, and the multi-GPU pipeline.
 """
 from __future__ import annotations
 
 import numpy as np
 
 from . import _lib
-from .analyzer import RETURN_TYPES, _dev
+from .analyzer import RETURN_TYPES, _buffer, _dev, check_corr_method, rank_ic
 from .grid import pack_bits, unpack_bits
 
 STATS = ["n", "mean", "std", "IR", "t"]
 
 
-def _buffer(bufs, name, shape, dtype, dev):
-    """A tensor of ``shape`` from the caller's buffer dict (allocated on first use, again when the
-    shape changes), or a fresh one."""
-    import torch
-    shape = tuple(int(s) for s in shape)
-    t = bufs.get(name) if bufs is not None else None
-    if t is None or tuple(t.shape) != shape or t.dtype is not dtype:
-        t = torch.empty(shape, dtype=dtype, device=dev)
-        if bufs is not None:
-            bufs[name] = t
-    return t
-
-
 def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zcols=None,
-                col_stride=None, dates_idx=None, year=None, bufs=None) -> dict:
+                col_stride=None, dates_idx=None, year=None, bufs=None,
+                corr_method="pearson") -> dict:
     """Device-level screen on grids.  ``base``: the panel, plane k of the screen at ``base +
     cols[k] * col_stride`` ([T][lda] each; ``col_stride`` defaults to T * lda); ``close`` [T][lda]
     with ``price_bits`` presence (the price rows of the forward returns); ``row_bits``: the row
@@ -47,14 +35,16 @@ def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zco
     One forward-return pass, one ``afm_xs_prepare_f64`` on a plane that is 0.0 on the rows and NaN
     elsewhere (the shared merge / dropna cascade and demeans; A <= 32768 as there), then the IC
     of every (date, column, return) and the summary.  ``dates_idx``: the evaluated dates (default:
-    those with rows); ``year`` [T]: calendar years for the per-year IR.  Pearson only; no layers
-    or top-k (use ``evaluate_grid`` on the columns that pass the screen).
+    those with rows); ``year`` [T]: calendar years for the per-year IR.  ``corr_method``: 'pearson'
+    or 'spearman' (the rank IC: the return ranks of a date are taken once for all columns).  No
+    layers or top-k (use ``evaluate_grid`` on the columns that pass the screen).
 
     Returns device tensors ``ic`` [nd][K][3], ``stats`` [K][3][5] (n, mean, std, IR, t over the
     non-NaN ICs), ``ir_year`` [nyears][K][3], ``nrows``, ``rows_idx``, and the host arrays
     ``dates_idx``, ``years``, ``year0``.  ``bufs``: a dict that keeps the work buffers between
     calls."""
     import torch
+    check_corr_method(corr_method)
     dev = close.device
     T, lda = close.shape
     f64, i32 = torch.float64, torch.int32
@@ -88,8 +78,12 @@ def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zco
     nd = len(dates_idx)
     d_t = torch.from_numpy(dates_idx).to(dev)
     ic = _buffer(bufs, "ic", (nd, K, 3), f64, dev)
-    call("afm_screen_ic_f64", base, col_stride, T, lda, cols_t, K, zs, zc_t, d_t, nd, rows,
-         rows_idx, nrows, ic)
+    if corr_method == "spearman":
+        rank_ic(call, base, col_stride, cols_t, K, zs, zc_t, d_t, nd, rows, rows_idx, nrows, ic,
+                bufs)
+    else:
+        call("afm_screen_ic_f64", base, col_stride, T, lda, cols_t, K, zs, zc_t, d_t, nd, rows,
+             rows_idx, nrows, ic)
     if year is not None and nd:
         yr = np.ascontiguousarray(np.asarray(year)[dates_idx], dtype=np.int32)
         y0, ny = int(yr.min()), int(yr.max() - yr.min() + 1)
@@ -106,8 +100,9 @@ def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zco
 
 
 class FactorScreen:
-    """``FactorScreen(factors_df, price_data, columns=None).run()``: the IC / IR screen of every
-    column of ``factors_df`` -- indexed (date, id), one column per factor, e.g. the reference's
+    """``FactorScreen(factors_df, price_data, columns=None, corr_method="pearson").run()``: the
+    IC / IR screen (Pearson, or with 'spearman' the rank IC, as the analyzer's ``corr_method``) of
+    every column of ``factors_df`` -- indexed (date, id), one column per factor, e.g. the reference's
     ``df_train_x`` -- against the forward returns of ``price_data`` (what ``AlphaSignalAnalyzer``
     takes: indexed (date, id), a ``close_price`` column).  The row set is the frame's rows; a NaN
     or inf cell is skipped for its own column only.  For a column without NaN the results are
@@ -115,10 +110,11 @@ class FactorScreen:
 
     After ``run()``: ``ic_df`` (date, factor, Type, IC; NaN ICs dropped; ordered by date, factor
     in column order, Type), ``ir_df`` (year, factor, Type, IR) and ``summary`` (factor, Type, n,
-    mean, std, IR, t; by \\|IR\\| descending, ties in column order, NaN last).  Pearson IC only;
-    layers and the top-k backtest are the analyzer's."""
+    mean, std, IR, t; by \\|IR\\| descending, ties in column order, NaN last).  Layers and the
+    top-k backtest are the analyzer's."""
 
-    def __init__(self, factors_df, price_data, columns=None):
+    def __init__(self, factors_df, price_data, columns=None, corr_method="pearson"):
+        self.corr_method = check_corr_method(corr_method)
         self.factors_df = factors_df
         self.columns = list(columns) if columns is not None else list(factors_df.columns)
         self.return_type = list(RETURN_TYPES)
@@ -155,7 +151,8 @@ class FactorScreen:
         pm = torch.zeros((T, lda), dtype=torch.bool, device=dev)
         pm[pt, pa] = True
         year = dates.astype("datetime64[Y]").astype(np.int64) + 1970
-        r = screen_grid(base, np.arange(K), close, pack_bits(pm), pack_bits(rm), A=A, year=year)
+        r = screen_grid(base, np.arange(K), close, pack_bits(pm), pack_bits(rm), A=A, year=year,
+                        corr_method=self.corr_method)
         r["dates"], r["ids"] = dates, ids
         self._res = r
         ic = r["ic"].cpu().numpy()                                   # [nd][K][3]

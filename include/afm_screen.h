@@ -8,8 +8,9 @@
  * per date (KKT:342-349) and whose IR is mean / std of the ICs per year (KKT:351-354).  All
  * columns of one frame share the rows, the forward returns and the per-date demeans, so those
  * are prepared once (afm_fwd_returns_f64, afm_xs_prepare_f64 with a signal plane that marks the
- * rows) and these two entry points evaluate every column on them.  Rank (Spearman) IC, decile
- * layers and the top-k backtest per factor are out of scope.
+ * rows) and these two entry points evaluate every column on them.  The rank (Spearman) IC of the
+ * same columns is afm_rankic.h's; decile layers and the top-k backtest per factor are out of
+ * scope.
  */
 #ifndef AFM_SCREEN_H
 #define AFM_SCREEN_H

@@ -1,7 +1,9 @@
 """Time the factor screen at the bench workload's train split (config C: 10,000 assets x 5,040
 days; the 97 z-scored feature columns on the z-score rows of the train dates, pipeline state after
 one step): the shared preparation, screen_ic_kernel alone, the summary alone, and -- for comparison
--- the loop the screen replaces, ``evaluate_grid`` once per column (8 calls, scaled to 97).
+-- the loop the screen replaces, ``evaluate_grid`` once per column (8 calls, scaled to 97).  The
+``rank`` step times the Spearman screen the same way: the return ranks (once per date), the rank
+IC kernel, the Pearson kernel for scale, and the ``evaluate_grid(corr_method='spearman')`` loop.
     python tools/screen_probe.py                 every step, each in a child process with its own
                                                  time limit; stops at the first failure
     python tools/screen_probe.py --step ic       one step in this process
@@ -14,7 +16,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "alpha-multi-factor-models_amd")]
 
-STEPS = {"prep": 420, "ic": 420, "summary": 420, "loop": 600}      # time limit, seconds
+STEPS = {"prep": 420, "ic": 420, "summary": 420, "loop": 600, "rank": 600}   # time limit, seconds
 HBM_TBS = 8.0                                                       # MI355X peak
 
 
@@ -135,6 +137,8 @@ def run_step(step, assets, days):
         print(f"screen_ic raw values (no z table): {ms_raw:.3f} ms -> "
               f"{panel / ms_raw / 1e9:.3f} TB/s", flush=True)
         return
+    if step == "rank":
+        return rank_step(s, b, q, ic, cells)
     ic()
     if step == "summary":
         stats = torch.empty((K, 3, 5), dtype=torch.float64, device=q["ic"].device)
@@ -172,6 +176,77 @@ def run_step(step, assets, days):
           f"{float(np.median(t_sig)):.3f} ms more) -> {per * K:.1f} ms for K = {K} columns, "
           f"{ncall} calls scaled", flush=True)
     print(f"loop ic of the {ncall} columns bit-equal to the screen's: {same}", flush=True)
+
+
+def rank_step(s, b, q, pearson_ic, cells):
+    """The Spearman screen: return ranks once per date, the rank IC of every (date, column); the
+    Pearson kernel for scale; the per-column ``evaluate_grid(corr_method='spearman')`` loop."""
+    import numpy as np
+    import torch
+    from afm.analyzer import evaluate_grid
+    from afm.grid import unpack_bits
+    pipe, call, T, lda = s["pipe"], s["call"], s["T"], s["lda"]
+    K, nd, dev = q["K"], q["nd"], q["ic"].device
+    words = call("afm_rank_scratch_words", lda)
+    scr = torch.empty(max(words, 1), dtype=torch.int64, device=dev)
+    rrank = torch.empty((3, T, lda), dtype=torch.int32, device=dev)
+    rsum = torch.empty((T, 3), dtype=torch.int64, device=dev)
+
+    def ranks():
+        call("afm_rank_returns_f64", T, lda, q["d_t"], nd, b["rows"], b["nrows"], rrank, rsum, scr)
+
+    def rank_ic():
+        call("afm_screen_rank_ic_f64", s["base"], s["stride"], T, lda, pipe.feat, K, pipe.zs, None,
+             q["d_t"], nd, b["rows"], b["rows_idx"], b["nrows"], rrank, rsum, scr, q["ic"])
+    ms_r = median_ms(ranks)
+    ms = median_ms(rank_ic)
+    ms_p = median_ms(pearson_ic)
+    rank_ic()
+    torch.cuda.synchronize()
+    ric = q["ic"].clone()
+    slow = int((rsum[torch.from_numpy(q["didx"]).long().to(dev)] < 0).any(dim=1).sum().item())
+    items = nd * K
+    # the sort of a date of the mean row count: runs as csrc/rankic.hip's run_rows splits them,
+    # a bitonic network of lg (lg + 1) / 2 passes over each run's power of two
+    rem, runs, passes = int(round(cells / max(nd, 1))), [], 0
+    while rem > 0:
+        length = min(rem, 16384) if rem >= 16384 else (1 << (rem.bit_length() - 1)
+                                                     if rem >= 2048 else rem)
+        p2 = max(2, 1 << (length - 1).bit_length())
+        lg = p2.bit_length() - 1
+        runs.append(p2)
+        passes += p2 * (lg * (lg + 1) // 2)
+        rem -= length
+    sort_bytes = items * passes * 8 * 2                      # every pass reads and writes a key
+    print(f"rank returns: {ms_r:.3f} ms for {nd} dates x 3 returns ({slow} dates with a "
+          f"non-finite return)", flush=True)
+    print(f"rank screen_ic: {ms:.3f} ms for {nd} dates, {cells} rows, K = {K} "
+          f"({items} workgroups, {ms * 1e3 / items * 256:.1f} us each on 256 CUs)", flush=True)
+    print(f"rank sort traffic: bitonic runs of {runs} keys at the mean row count, {passes} "
+          f"key-passes -> {sort_bytes / 1e12:.2f} TB of LDS reads + writes at most, "
+          f"{sort_bytes / ms / 1e9:.1f} TB/s if the sort were the whole kernel", flush=True)
+    print(f"pearson screen_ic, same inputs: {ms_p:.3f} ms", flush=True)
+    rowm = unpack_bits(s["rb"], T)
+    nan = torch.full((T, lda), float("nan"), dtype=torch.float64, device=dev)
+    ncall, t_eval, same = 8, [], True
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    for k in range(ncall):
+        c = int(pipe.feat[k].item())
+        z = (pipe.out[c, :T] - pipe.zs[k, :, 0]) * pipe.zs[k, :, 1]
+        sig = torch.where(rowm, z, nan)
+        ev[0].record()
+        one = evaluate_grid(sig, s["close"], s["pb"], A=s["A"], dates_idx=q["didx"],
+                            year=s["year"], corr_method="spearman")
+        ev[1].record()
+        torch.cuda.synchronize()
+        t_eval.append(ev[0].elapsed_time(ev[1]))
+        a, g = one["ic"].cpu().numpy(), ric[:, k, :].cpu().numpy()
+        same = same and bool(((a == g) | (np.isnan(a) & np.isnan(g))).all())
+    per = float(np.median(t_eval))
+    print(f"rank loop evaluate_grid(corr_method='spearman'): {per:.3f} ms per column (median of "
+          f"{ncall}) -> {per * K:.1f} ms for K = {K} columns, {ncall} calls scaled; the single "
+          f"pass: {ms_r + ms:.3f} ms ({per * K / (ms_r + ms):.1f}x)", flush=True)
+    print(f"rank loop ic of the {ncall} columns bit-equal to the screen's: {same}", flush=True)
 
 
 def main():
