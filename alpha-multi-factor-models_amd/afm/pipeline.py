@@ -109,9 +109,9 @@ class PipelineConfig:
     features: tuple | None = None
     # stream placement (moves work between streams only; the outputs are bitwise the same):
     # labels_side -- one GPU: the two label planes on a side stream beside the factor kernel;
-    # fm_fork -- one GPU: where the FM per-date Grams fork off the main stream ("gram", "predict",
-    # "analyzer" or "rebalance"; measured best: "predict"); main_priority -- the main stream at
-    # high priority
+    # fm_fork -- one GPU: where the FM per-date Grams fork off the main stream ("pool": straight
+    # after the pooled Gram's partial kernel, ahead of its trees; "gram", "predict", "analyzer" or
+    # "rebalance": after that stage); main_priority -- the main stream at high priority
     labels_side: bool = True
     fm_fork: str = "predict"
     main_priority: bool = True
@@ -246,7 +246,7 @@ class Pipeline:
             raise ValueError(f"{W} ranks: the GPU count must divide {N_BLOCKS}")
         self.blk = blk = block_assets(lda)
         self.rb_per_blk = blk // 64
-        if self.rb_per_blk > 32:          # afm_gram_tree_f64 merges at most 32 leaves a level
+        if self.rb_per_blk > 32:          # the Gram trees merge at most 32 leaves a level
             raise ValueError(f"{A} assets: the pooled-Gram tree holds at most "
                              f"{N_BLOCKS * 32 * 64} assets ({N_BLOCKS} blocks x 32 row-blocks "
                              f"of 64)")
@@ -284,8 +284,6 @@ class Pipeline:
         self.asset_ok = torch.empty(lda_r, **i32)
         self.pe = pe = self.ctx.call("afm_zgram_part_bytes", p) // 8
         self.pool_part = torch.empty((nrb, N_CHUNKS, pe), **f64)
-        self.pool_c1 = torch.empty((nrb * (N_CHUNKS // CHUNK_TREE[0]), pe), **f64)
-        self.pool_rb = torch.empty((nrb, pe), **f64)
         self.pool_blk = torch.zeros((self.nblk_r + 1, pe), **f64)   # + the train_end subtree
         self.pool_all = torch.zeros((N_BLOCKS, pe), **f64)
         self.te_part = torch.zeros((self.nblk_r, pe), **f64)
@@ -305,12 +303,13 @@ class Pipeline:
                                        device=self.full.device)
         self.pef = pef = self.ctx.call("afm_zgram_part_bytes", pf) // 8
         self.fm_part = torch.zeros((T, self.nblk_r, pef), **f64)
-        self.fm_sub = torch.zeros((T, pef), **f64)      # this shard's subtree per date
+        # this shard's subtree per date (N > 1: what the exchange sends; one GPU solves straight
+        # from fm_part)
+        self.fm_sub = torch.zeros((T if W > 1 else 0, pef), **f64)
         self.fdr = [even_range(T, W, q) for q in range(W)]   # FM dates owned by each rank
         fd0, fd1 = self.fdr[self.rank]
         self.fd0, self.fnd = fd0, fd1 - fd0
         self.fnd_max = max(b - a for a, b in self.fdr)
-        self.fm_gram = torch.empty((max(self.fnd, 1), pf + 2, pf + 2), **f64)
         self.fm_shift = torch.zeros((max(self.fnd, 1), pf + 2), **f64)
         self.fm_beta_own = torch.full((self.fnd_max, pf + 1), float("nan"), **f64)
         self.fm_nobs_own = torch.zeros(self.fnd_max, **f64)
@@ -417,8 +416,8 @@ class Pipeline:
         """The step's streams, created in the order main, side, side2, side3."""
         import torch
         c, W, dev = self.cfg, self.W, self.full.device
-        if c.fm_fork not in ("gram", "predict", "analyzer", "rebalance"):
-            raise ValueError(f"fm_fork={c.fm_fork!r}: expected gram, predict, analyzer or "
+        if c.fm_fork not in ("pool", "gram", "predict", "analyzer", "rebalance"):
+            raise ValueError(f"fm_fork={c.fm_fork!r}: expected pool, gram, predict, analyzer or "
                              "rebalance")
         self.ncu = torch.cuda.get_device_properties(dev).multi_processor_count
         self.main = torch.cuda.Stream(device=dev, priority=-8 if c.main_priority else 0)
@@ -508,18 +507,21 @@ class Pipeline:
         call, T, lda_r, p = self.ctx.call, self.T, self.lda_r, self.p
         call("afm_zscore_stats_f64", self.out, T * lda_r, T, lda_r, self.feat, p, self.alldf, 0,
              self.sp.tr1, self.mu, self.sd)
-        call("afm_zstats_finalize_f64", self.mu, self.sd, p, lda_r, self.zs, self.asset_ok)
-        self._zrows(0, nw, nt)
+        call("afm_zstats_rows_f64", self.mu, self.sd, p, lda_r, self.zs, self.asset_ok, nw,
+             self.frows, 0, nt, self.zrows)
 
-    def _pooled_blocks(self, t0, nt, bufs=None, mark=None):
+    def _pooled_blocks(self, t0, nt, bufs=None, mark=None, after_pool=None):
         """This shard's pooled-Gram block results (rows of the dates [t0, t0 + nt)): row-block x
-        chunk partials, then the tree -- the chunks of a row-block (32, then 2), the row-blocks
-        of an asset block -> pool_blk[0:nblk_r], or in the buffers ``bufs`` (part, c1, rb, blk)
-        instead of the step's."""
+        chunk partials, then the tree in one launch -- the chunks of a row-block (32, then 2), the
+        row-blocks of an asset block -> pool_blk[0:nblk_r] (every block written: zeros where the
+        shard has no row-block), or in the buffers ``bufs`` (part, blk) instead of the step's.
+        ``after_pool()`` runs between the partial kernel's launch and the tree's."""
         call, T, lda, p = self.ctx.call, self.T, self.lda_r, self.p
-        part, c1b, rb, blk = bufs or (self.pool_part, self.pool_c1, self.pool_rb, self.pool_blk)
-        blk.zero_()
+        part, blk = bufs or (self.pool_part, self.pool_blk)
         if self.nrb == 0:
+            blk[:self.nblk_r].zero_()
+            if after_pool is not None:
+                after_pool()
             return
         if mark is not None:
             mark("k_gram", 0)
@@ -527,38 +529,43 @@ class Pipeline:
              self.zrows, t0, nt, 0, self.nrb, self.A_r, N_CHUNKS, part, 0)
         if mark is not None:
             mark("k_gram", 1)
+        if after_pool is not None:
+            after_pool()
         c1, c2 = CHUNK_TREE
-        call("afm_gram_tree_f64", p, part, self.nrb * N_CHUNKS, c1, 0, c1b)
-        call("afm_gram_tree_f64", p, c1b, self.nrb * c2, c2, 0, rb)
-        call("afm_gram_tree_f64", p, rb, self.nrb, self.rb_per_blk, 0, blk)
+        call("afm_gram_tree3_f64", p, part, self.nrb, c1, c2, self.rb_per_blk, self.nblk_r, blk)
 
     def _te_subtree(self, t):
-        """This shard's subtree of the train_end date's Gram -> pool_blk[nblk_r]."""
+        """This shard's block partials of the train_end date's Gram -> te_part; N > 1: their
+        subtree -> pool_blk[nblk_r] (what the exchange sends; one GPU merges the block partials
+        in the final launch: the tree over its 8 leaves is the subtree, then a one-leaf level)."""
         call, T, lda, p = self.ctx.call, self.T, self.lda_r, self.p
         if self.nrb == 0:
             return
         call("afm_zgram_f64", self.out, T * lda, lda, self.feat, None, p, TARGET, self.zs, p,
              self.zrows, t, 1, self.nblk_r, 0, self.blk, self.A_r, self.te_part, 0)
-        call("afm_gram_tree_f64", p, self.te_part, self.nblk_r, self.nblk_r, 0,
-             self.pool_blk[self.nblk_r:])
+        if self.W > 1:
+            call("afm_gram_tree_f64", p, self.te_part, self.nblk_r, self.nblk_r, 0,
+                 self.pool_blk[self.nblk_r:])
 
     def _fm_local(self):
-        """This shard's per-date FM30 partials over the z-score rows, merged over its blocks ->
-        fm_sub [T]."""
+        """This shard's per-date FM30 partials over the z-score rows -> fm_part [T][nblk_r];
+        N > 1: merged over its blocks -> fm_sub [T]."""
         call, T, lda, pf = self.ctx.call, self.T, self.lda_r, self.pf
         if self.nrb == 0:
             return
         call("afm_zgram_f64", self.out, T * lda, lda, self.fm_cols, None, pf, TARGET, None, 0,
              self.zrows, 0, T, self.nblk_r, 0, self.blk, self.A_r, self.fm_part, self.fm_grid)
-        call("afm_gram_tree_f64", pf, self.fm_part, T * self.nblk_r, self.nblk_r, 0, self.fm_sub)
+        if self.W > 1:
+            call("afm_gram_tree_f64", pf, self.fm_part, T * self.nblk_r, self.nblk_r, 0,
+                 self.fm_sub)
 
-    def _fm_solve(self, sub):
-        """Owned dates: the rank subtrees ``sub`` [fnd][W][part] -> Grams, solves."""
-        call, pf = self.ctx.call, self.pf
+    def _fm_solve(self, leaves, per):
+        """Owned dates: each date's ``per`` partials ``leaves`` [fnd][per][part] merged over the
+        fixed tree while the solve loads them -- N > 1: the W rank subtrees; one GPU: the block
+        partials themselves (the tree over the 8 blocks, then a one-leaf level)."""
         if self.fnd > 0:
-            call("afm_gram_tree_f64", pf, sub, self.fnd * self.W, self.W, 1, self.fm_gram)
-            call("afm_ols_solve_f64", self.fm_gram, self.fm_shift, pf, self.fnd, self.cfg.tol,
-                 self.fm_beta_own, self.fm_nobs_own, self.fm_rank_own)
+            self.ctx.call("afm_ols_solve_parts_f64", leaves, per, self.fm_shift, self.pf, self.fnd,
+                          self.cfg.tol, self.fm_beta_own, self.fm_nobs_own, self.fm_rank_own)
 
     def _fm_stats(self):
         self.ctx.call("afm_fama_macbeth_f64", self.fm_beta, self.fm_rank, self.T, self.pf + 1,
@@ -566,19 +573,18 @@ class Pipeline:
 
     # ---- the factor stage's three paths --------------------------------------------------------
     def _factors_one_pass(self, lab_side, mark):
-        """The factor panel in one call on the main stream, then the all_df rows.  One GPU: the
+        """The factor panel and the all_df rows in one call on the main stream.  One GPU: the
         two label planes on the second side stream, enqueued after the factor kernel (it runs
         on the CUs the factor workgroups leave free); the z statistics wait for them."""
         g = self.g
         if self.A_r > 0:
             mark("k_factor", 0)
-            self.ctx.call("afm_factors_f64", self.T, self.A_r, self.lda_r, g.close, g.volume,
+            self.ctx.call("afm_factors_rows_f64", self.T, self.A_r, self.lda_r, g.close, g.volume,
                           None if lab_side else g.ret1d, None if lab_side else g.excess, g.vbits,
-                          self.out, self.nanfree, self.finite)
+                          self.out, self.nanfree, self.finite, self.alldf, self.frows)
             mark("k_factor", 1)
             if lab_side:
                 self._labels(self.side2)
-            self._last_obs_rows()
         mark("factors", 1)
 
     def _factors_streamed(self, lab_side, mark):
@@ -716,9 +722,13 @@ class Pipeline:
         then the block level of the tree), train_end's Gram added once more."""
         call, sp, p, W = self.ctx.call, self.sp, self.p, self.W
         mark("xs_gram", 0)
-        self._pooled_blocks(0, sp.v1, mark=mark)                # train + valid rows
-        if sp.dup:                                              # train_end counted twice
+        # train_end counted twice: its Gram first (it needs the z statistics and rows only), so
+        # that no kernel with a whole CU's LDS follows the pooled kernel and the FM Grams, which
+        # cannot share a CU with it, may start there
+        if sp.dup:
             self._te_subtree(sp.tr1 - 1)
+        self._pooled_blocks(0, sp.v1, mark=mark,                # train + valid rows
+                            after_pool=lambda: self._fork_fm("pool", mark))
         if W > 1:
             mark("exchange", 0)
             gb = self.comm.all_gather(self.pool_blk)            # [W][nblk_r + 1][part]
@@ -727,11 +737,9 @@ class Pipeline:
             mark("exchange", 1)
             blocks, te_leaves, nte = self.pool_all, self.te_all, W
         else:
-            blocks, te_leaves, nte = self.pool_blk, self.pool_blk[self.nblk_r:], 1
-        call("afm_gram_tree_f64", p, blocks, N_BLOCKS, N_BLOCKS, 1, self.pool_g)
-        if sp.dup:
-            call("afm_gram_tree_f64", p, te_leaves, nte, nte, 1, self.te_gram)
-            call("afm_vec_add_f64", self.p2 * self.p2, self.te_gram, self.pool_g)
+            blocks, te_leaves, nte = self.pool_blk, self.te_part, self.nblk_r
+        call("afm_gram_final_f64", p, blocks, N_BLOCKS, te_leaves if sp.dup else None, nte,
+             self.pool_g, self.te_gram)
         mark("xs_gram", 1)
 
     def _fork_fm(self, at, mark):
@@ -748,7 +756,7 @@ class Pipeline:
             mark("fm", 0)
             self._fm_local()
             if self.W == 1:
-                self._fm_solve(self.fm_sub)
+                self._fm_solve(self.fm_part, self.nblk_r)
                 self._fm_stats()
             mark("fm", 1)
 
@@ -929,7 +937,7 @@ class Pipeline:
         recv = self.comm.all_to_all(self.fm_sub, [b - a for a, b in self.fdr],
                                     [self.fnd] * W)                          # [W * fnd][part]
         sub = recv.view(W, self.fnd, self.pef).transpose(0, 1).contiguous()   # [fnd][W][part]
-        self._fm_solve(sub)
+        self._fm_solve(sub, W)
         got = self.comm.all_gather_packed([self.fm_beta_own, self.fm_nobs_own, self.fm_rank_own])
         self._place_shares("fm", self.fdr, got, (self.fm_beta, self.fm_nobs, self.fm_rank))
         self._fm_stats()
@@ -980,7 +988,7 @@ class Pipeline:
         """The pooled Gram of the z-score rows of the dates [t0, t0 + nt) -> gram [1][p+2][p+2]:
         ``_pooled_blocks`` in the buffers ``bufs`` (not the step's) + the block level."""
         self._pooled_blocks(t0, nt, bufs)
-        self.ctx.call("afm_gram_tree_f64", self.p, bufs[3], N_BLOCKS, N_BLOCKS, 1, gram)
+        self.ctx.call("afm_gram_final_f64", self.p, bufs[1], N_BLOCKS, None, 0, gram, None)
 
     def lasso_cv(self, alphas=None, *, n_alphas: int = 100, eps: float = 1e-3) -> dict:
         """Validation-scored alpha selection on the last ``step()``'s panel (one GPU): the
@@ -1004,8 +1012,7 @@ class Pipeline:
             raise ValueError("lasso_cv(): the panel has no assets")
         c, sp, p = self.cfg, self.sp, self.p
         if getattr(self, "_cv_bufs", None) is None:
-            self._cv_bufs = tuple(torch.empty_like(b) for b in (self.pool_part, self.pool_c1,
-                                                                self.pool_rb, self.pool_blk))
+            self._cv_bufs = tuple(torch.empty_like(b) for b in (self.pool_part, self.pool_blk))
             self._cv_gram = torch.empty((2, self.p2, self.p2), dtype=torch.float64,
                                         device=self.out.device)
         gram, shift = self._cv_gram, self.pool_s.expand(2, self.p2).contiguous()

@@ -39,6 +39,7 @@
 //
 // Algorithmic traffic per present asset-day: 32 B of inputs read + 98 x 8 B written = 816 B.
 #include "afm_internal.h"
+#include "afm_seams.h"
 
 #include <type_traits>
 
@@ -2126,6 +2127,39 @@ __global__ __launch_bounds__(256) void masks_kernel(int64_t nwords, int64_t lda,
     if (finite) finite[i] = v & ~bm;
 }
 
+// masks_kernel over every word of the series, and drop_last_obs_kernel of both masks, in ONE
+// launch: alldf = nanfree, frows = finite without the asset's last present day.  Thread (c, a)
+// clears that day's bit when no later word of the asset has a present day (one load for an asset
+// present to the end of the series).
+__global__ __launch_bounds__(256) void masks_rows_kernel(int64_t nwords, int64_t lda, int types,
+                                                         const uint64_t* vbits,
+                                                         const uint64_t* nanpart,
+                                                         const uint64_t* badpart, uint64_t* nanfree,
+                                                         uint64_t* finite, uint64_t* alldf,
+                                                         uint64_t* frows) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t n = nwords * lda;
+    if (i >= n) return;
+    u64 nm = 0ull, bm = 0ull;
+    for (int t = 0; t < types; ++t) {
+        nm |= nanpart[t * n + i];
+        bm |= badpart[t * n + i];
+    }
+    const u64 v = vbits[i];
+    const int64_t c = i / lda, a = i - c * lda;
+    u64 keep = ~0ull;
+    if (v) {
+        bool later = false;
+        for (int64_t cc = nwords - 1; cc > c && !later; --cc) later = vbits[cc * lda + a] != 0ull;
+        if (!later) keep = ~(1ull << (63 - __builtin_clzll(v)));
+    }
+    const u64 nf = v & ~nm, fi = v & ~bm;
+    nanfree[i] = nf;
+    finite[i] = fi;
+    alldf[i] = nf & keep;
+    frows[i] = fi & keep;
+}
+
 // target = excess_ret1d.shift(-1), tmr_ret1d = ret1d.shift(-1) (No-talib.py:90-91): the value of
 // the asset's NEXT present day, NaN on its last one.  One thread per (asset, 64-day presence
 // word): the word is walked backwards carrying the next present day's pair, so every load and
@@ -2282,7 +2316,10 @@ static int factors_slab(afm_ctx* ctx, int64_t T, int64_t A, int64_t lda, int64_t
                         const double* close, const double* volume, const double* ret1d,
                         const double* excess, const uint64_t* valid_bits, double* out,
                         uint64_t* nanfree_bits, uint64_t* finite_bits, double* state,
-                        bool full = false, uint64_t* ext_part = nullptr) {
+                        bool full = false, uint64_t* ext_part = nullptr,
+                        uint64_t* alldf_bits = nullptr, uint64_t* frows_bits = nullptr) {
+    // alldf_bits / frows_bits (whole series only): the masks without each asset's last present
+    // day, from the masks' own launch (masks_rows_kernel)
     // ext_part: the caller's buffer for the mask partials (afm_factors_part_words); the masks
     // are then left to afm_factor_masks_f64
     // full: out / nanfree / finite are the whole [T]-date panel and bit words (the slab's rows
@@ -2373,9 +2410,14 @@ static int factors_slab(afm_ctx* ctx, int64_t T, int64_t A, int64_t lda, int64_t
     const int64_t nw = nwords * lda;
     // columns past A (lda padding) carry no presence: their mask words come from valid_bits
     // (zero there), and the factor kernel never ran on blocks past ceil(A/64)
-    hipLaunchKernelGGL(afm::masks_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0,
-                       ctx->stream, nwords, lda, nparts, valid_bits + (t0 / 64) * lda, part,
-                       part + nparts * nw, nanfree_bits, finite_bits);
+    if (alldf_bits)
+        hipLaunchKernelGGL(afm::masks_rows_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256),
+                           0, ctx->stream, nwords, lda, nparts, valid_bits, part,
+                           part + nparts * nw, nanfree_bits, finite_bits, alldf_bits, frows_bits);
+    else
+        hipLaunchKernelGGL(afm::masks_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0,
+                           ctx->stream, nwords, lda, nparts, valid_bits + (t0 / 64) * lda, part,
+                           part + nparts * nw, nanfree_bits, finite_bits);
     AFM_HIP(hipGetLastError());
     if (excess) {                  // NULL: the caller runs afm_labels_f64 (e.g. on another stream)
         dim3 g2((unsigned)((lda + 255) / 256), (unsigned)((t1 - 1) / 64 - t0 / 64 + 1));
@@ -2400,6 +2442,25 @@ extern "C" int afm_factors_f64(afm_ctx* ctx, int64_t T, int64_t A, int64_t lda,
     AFM_CHECK_ARG(T <= (int64_t)1 << 31, "T too large");
     return factors_slab(ctx, T, A, lda, 0, T, close, volume, ret1d, excess, valid_bits, out,
                         nanfree_bits, finite_bits, nullptr);
+}
+
+extern "C" int afm_factors_rows_f64(afm_ctx* ctx, int64_t T, int64_t A, int64_t lda,
+                                    const double* close, const double* volume,
+                                    const double* ret1d, const double* excess,
+                                    const uint64_t* valid_bits, double* out,
+                                    uint64_t* nanfree_bits, uint64_t* finite_bits,
+                                    uint64_t* alldf_bits, uint64_t* frows_bits) {
+    AFM_CTX(ctx);
+    AFM_CHECK_ARG(T > 0 && A > 0, "T and A must be positive");
+    AFM_CHECK_ARG(lda >= A && lda % 64 == 0, "lda must be a multiple of 64 and >= A");
+    AFM_CHECK_ARG(close && volume && valid_bits && out && nanfree_bits && finite_bits &&
+                      alldf_bits && frows_bits, "null buffer");
+    AFM_CHECK_ARG((ret1d == nullptr) == (excess == nullptr),
+                  "ret1d and excess are both given or both NULL");
+    AFM_CHECK_ARG(T <= (int64_t)1 << 31, "T too large");
+    return factors_slab(ctx, T, A, lda, 0, T, close, volume, ret1d, excess, valid_bits, out,
+                        nanfree_bits, finite_bits, nullptr, false, nullptr, alldf_bits,
+                        frows_bits);
 }
 
 extern "C" int64_t afm_factors_state_bytes(afm_ctx* ctx, int64_t A) {

@@ -28,6 +28,8 @@
 // lets the producers run up to S blocks ahead (S = 3 at p = 96).
 // Algorithmic work per segment: rows * (p+2)(p+3) flops over 8(p+1) B per row.
 #include "afm_internal.h"
+#include "afm_seams.h"
+#include "zgram_layout.h"
 
 #include <cstdlib>
 
@@ -691,9 +693,9 @@ struct SolveArgs {
 
 constexpr int kMaxP = kMaxF - 2;
 
-__global__ __launch_bounds__(kThreads) void ols_solve_kernel(SolveArgs s) {
-    AFM_TAIL_PRIO_SET();
-    extern __shared__ __attribute__((aligned(16))) double M[];    // packed lower triangle
+// the solve of segment blockIdx.x from its Gram G [pg + 2][pg + 2] (global or LDS); M: the
+// packed lower triangle, (p + 1)(p + 2) / 2 doubles of LDS
+__device__ __forceinline__ void ols_solve_segment(const SolveArgs& s, const double* G, double* M) {
     __shared__ double dsc[kMaxP + 1];
     __shared__ double dk[kMaxP];
     __shared__ double mean[kMaxP + 2];
@@ -704,7 +706,6 @@ __global__ __launch_bounds__(kThreads) void ols_solve_kernel(SolveArgs s) {
     const int p = s.p, q = p + 1;
     const int p2 = s.pg + 2;                         // Gram dimension
     auto row = [](int i) { return i * (i + 1) / 2; };      // offset of row i
-    const double* G = s.gram + (int64_t)blockIdx.x * p2 * p2;
     const double* sf = s.shift + (int64_t)blockIdx.x * p2;
     for (int r = tid; r <= q; r += kThreads)
         gx[r] = r == 0 ? 0 : (r == q ? s.pg + 1 : (s.sel ? 1 + s.sel[r - 1] : r));
@@ -785,6 +786,39 @@ __global__ __launch_bounds__(kThreads) void ols_solve_kernel(SolveArgs s) {
             s.rank[blockIdx.x] = rk;
         }
     }
+}
+
+__global__ __launch_bounds__(kThreads) void ols_solve_kernel(SolveArgs s) {
+    AFM_TAIL_PRIO_SET();
+    extern __shared__ __attribute__((aligned(16))) double M[];    // packed lower triangle
+    ols_solve_segment(s, s.gram + (int64_t)blockIdx.x * (s.pg + 2) * (s.pg + 2), M);
+}
+
+// The solve straight from a segment's `per` partial Grams (zgram.hip's layout, raw moments): the
+// segment's symmetric Gram is built in LDS -- per element the tree of afm_gram_tree_f64's final
+// launch (zgram_tree32 over the leaves [seg * per, + per)) -- and solved from there, without the
+// merge launch and the Gram's round trip through memory.  s.gram: the partials [nseg][per][pe].
+__global__ __launch_bounds__(kThreads) void ols_solve_parts_kernel(SolveArgs s, int per, int pe) {
+    AFM_TAIL_PRIO_SET();
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int p2 = s.pg + 2;
+    double* G = lds;                                 // [p2][p2]
+    double* M = lds + p2 * p2;                       // packed lower triangle
+    const double* src = s.gram + (int64_t)blockIdx.x * per * pe;
+    for (int e = threadIdx.x; e < pe; e += kThreads) {
+        double v[32];
+#pragma unroll
+        for (int b = 0; b < 32; ++b) v[b] = b < per ? src[(int64_t)b * pe + e] : 0.0;
+        const double g = zgram_tree32(v, per);
+        int row, col;
+        zgram_elem_rc(e, row, col);
+        if (row < p2 && col < p2) {
+            G[row * p2 + col] = g;
+            G[col * p2 + row] = g;
+        }
+    }
+    __syncthreads();
+    ols_solve_segment(s, G, M);
 }
 
 // ---- exact (Chan) combination of per-segment shifted moments ----------------------------------
@@ -1070,6 +1104,23 @@ extern "C" int afm_ols_solve_f64(afm_ctx* ctx, const double* gram, const double*
     AFM_HIP(afm_lds_opt_in(ctx, (const void*)ols_solve_kernel, (int)lds));
     hipLaunchKernelGGL(ols_solve_kernel, dim3((unsigned)nseg), dim3(kThreads), lds, ctx->stream,
                        s);
+    AFM_HIP(hipGetLastError());
+    return AFM_OK;
+}
+
+extern "C" int afm_ols_solve_parts_f64(afm_ctx* ctx, const double* parts, int per,
+                                       const double* shift, int p, int64_t nseg, double tol,
+                                       double* beta, double* nobs, int32_t* rank) {
+    AFM_CTX(ctx);
+    AFM_CHECK_ARG(p >= 1 && p <= 106, "need 1 <= p <= 106");
+    AFM_CHECK_ARG(per >= 1 && per <= 32, "need 1 <= per <= 32");
+    AFM_CHECK_ARG(parts && shift && beta && nobs && rank, "null buffer");
+    if (nseg <= 0) return AFM_OK;
+    SolveArgs s{parts, shift, p, tol, nullptr, p, beta, nobs, rank};
+    const size_t lds = sizeof(double) * ((size_t)(p + 2) * (p + 2) + (size_t)(p + 1) * (p + 2) / 2);
+    AFM_HIP(afm_lds_opt_in(ctx, (const void*)ols_solve_parts_kernel, (int)lds));
+    hipLaunchKernelGGL(ols_solve_parts_kernel, dim3((unsigned)nseg), dim3(kThreads), lds,
+                       ctx->stream, s, per, zgram_pe(zgram_nt(p)));
     AFM_HIP(hipGetLastError());
     return AFM_OK;
 }

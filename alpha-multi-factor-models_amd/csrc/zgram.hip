@@ -24,6 +24,8 @@
 // Algorithmic work of zgram: rows * (p+2)(p+3) flops per date; bytes: 8(p+1) per
 // row from HBM (+16 p per row of {mu, 1/sigma}, L2-resident per asset block: blocks map to XCDs).
 #include "afm_internal.h"
+#include "afm_seams.h"
+#include "zgram_layout.h"
 
 #include <cstdlib>
 
@@ -603,11 +605,7 @@ __global__ __launch_bounds__(256) void tree_merge_kernel(const double* in, int64
         double v[32];
 #pragma unroll
         for (int b = 0; b < 32; ++b) v[b] = b < n ? src[(int64_t)b * Cf::PE + e] : 0.0;
-#pragma unroll
-        for (int s = 1; s < 32; s *= 2)
-#pragma unroll
-            for (int i = 0; i + s < 32; i += 2 * s)
-                if (i + s < n) v[i] = v[i] + v[i + s];
+        zgram_tree32(v, n);
         if (!final_out) {
             out[gi * Cf::PE + e] = v[0];
         } else {
@@ -623,14 +621,93 @@ __global__ __launch_bounds__(256) void tree_merge_kernel(const double* in, int64
     }
 }
 
+// The pooled leaves [nrb][c2][c1] -> the asset-block partials in ONE launch: per element the trees
+// of three tree_merge_kernel launches (groups of c1 chunks, the c2 results of a row-block, the
+// row-blocks of a block), each level through zgram_tree32 with the leaf counts those launches
+// see.  Workgroup (x, b): the 64 elements [64x, 64x + 64) of block b; the level results pass
+// through LDS, a wave per (row-block, chunk group), then per row-block.  A block without
+// row-blocks is written as zeros, so the output needs no clearing.
+constexpr int kT3Waves = 8;
+constexpr int kT3Items = 64;                 // c2 * rb_per_blk of one block at most
+template <int NT>
+__global__ __launch_bounds__(kT3Waves * 64) void tree3_kernel(const double* in, int nrb, int c1,
+                                                              int c2, int rb_per_blk,
+                                                              double* out) {
+    using Cf = ZCfg<NT>;
+    __shared__ double s1[kT3Items][64];
+    __shared__ double s2[32][64];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int e = blockIdx.x * 64 + lane;
+    const int b = blockIdx.y;
+    const int r0 = b * rb_per_blk;
+    const int n = nrb - r0 < rb_per_blk ? nrb - r0 : rb_per_blk;     // row-blocks of this block
+    if (n <= 0) {
+        if (wave == 0) out[(int64_t)b * Cf::PE + e] = 0.0;
+        return;
+    }
+    double v[32];
+    for (int it = wave; it < n * c2; it += kT3Waves) {               // chunk groups: c1 leaves
+        const double* src = in + ((int64_t)r0 * c2 + it) * c1 * Cf::PE + e;
+#pragma unroll
+        for (int k = 0; k < 32; ++k) v[k] = k < c1 ? src[(int64_t)k * Cf::PE] : 0.0;
+        s1[it][lane] = zgram_tree32(v, c1);
+    }
+    __syncthreads();
+    for (int r = wave; r < n; r += kT3Waves) {                       // row-blocks: c2 results
+#pragma unroll
+        for (int k = 0; k < 32; ++k) v[k] = k < c2 ? s1[r * c2 + k][lane] : 0.0;
+        s2[r][lane] = zgram_tree32(v, c2);
+    }
+    __syncthreads();
+    if (wave == 0) {                                                 // the block: n row-blocks
+#pragma unroll
+        for (int k = 0; k < 32; ++k) v[k] = k < n ? s2[k][lane] : 0.0;
+        out[(int64_t)b * Cf::PE + e] = zgram_tree32(v, n);
+    }
+}
+
+// The block level in ONE launch: G = the final tree over the nblk block partials, Gte = the final
+// tree over the nte train_end leaves (te null: none), G += Gte -- what two final tree_merge_kernel
+// launches and vec_add_kernel (y = y + x) leave in G and Gte.
+template <int NT>
+__global__ __launch_bounds__(256) void gram_final_kernel(const double* blocks, int nblk,
+                                                         const double* te, int nte, int p2,
+                                                         double* G, double* Gte) {
+    using Cf = ZCfg<NT>;
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    double v[32];
+#pragma unroll
+    for (int k = 0; k < 32; ++k) v[k] = k < nblk ? blocks[(int64_t)k * Cf::PE + e] : 0.0;
+    double g = zgram_tree32(v, nblk);
+    int row, col;
+    zgram_elem_rc(e, row, col);
+    const bool in = row < p2 && col < p2;
+    if (te) {
+#pragma unroll
+        for (int k = 0; k < 32; ++k) v[k] = k < nte ? te[(int64_t)k * Cf::PE + e] : 0.0;
+        const double t = zgram_tree32(v, nte);
+        if (in) {
+            Gte[row * p2 + col] = t;
+            Gte[col * p2 + row] = t;
+        }
+        g = g + t;
+    }
+    if (in) {
+        G[row * p2 + col] = g;
+        G[col * p2 + row] = g;
+    }
+}
+
 // ---- z-score statistics -> {mu, 1/sigma} and the surviving assets ------------------------------
-__global__ __launch_bounds__(256) void zstats_finalize_kernel(const double* mu, const double* sd,
-                                                              int K, int64_t lda, double* zs,
-                                                              int32_t* asset_ok) {
-    const int64_t a = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (a >= lda) return;
+// asset a: its zs rows {mu, 1/sigma} of the features k0, k0 + kstep, .. < K (k0 = 0: and the
+// identity row K); returns whether every one of them is usable (asset_ok over all features)
+__device__ __forceinline__ int zstats_asset(const double* __restrict__ mu,
+                                            const double* __restrict__ sd, int K, int64_t lda,
+                                            int64_t a, double* __restrict__ zs, int k0 = 0,
+                                            int kstep = 1) {
     int ok = 1;
-    for (int k = 0; k < K; ++k) {
+    for (int k = k0; k < K; k += kstep) {
         const double m = mu[(int64_t)k * lda + a], s = sd[(int64_t)k * lda + a];
         const double r = 1.0 / s;
         // NaN sigma fails s > 0.  A subnormal sigma (< 2^-1024, 1/sigma overflows) also drops the
@@ -643,11 +720,29 @@ __global__ __launch_bounds__(256) void zstats_finalize_kernel(const double* mu, 
         v.y = okk ? r : 0.0;
         reinterpret_cast<double2*>(zs)[(int64_t)k * lda + a] = v;
     }
-    double2 one;
-    one.x = 0.0;
-    one.y = 1.0;
-    reinterpret_cast<double2*>(zs)[(int64_t)K * lda + a] = one;   // row K: y passes unchanged
-    asset_ok[a] = ok;
+    if (k0 == 0) {
+        double2 one;
+        one.x = 0.0;
+        one.y = 1.0;
+        reinterpret_cast<double2*>(zs)[(int64_t)K * lda + a] = one;   // row K: y passes unchanged
+    }
+    return ok;
+}
+
+// word c (dates [64c, 64c + 64)) restricted to the dates [t0, t1)
+__device__ __forceinline__ u64 date_range_word(u64 w, int64_t c, int64_t t0, int64_t t1) {
+    const int64_t d0 = c << 6;
+    if (t0 > d0) w &= t0 - d0 >= 64 ? 0ull : (~0ull << (t0 - d0));
+    if (t1 - d0 < 64) w &= t1 <= d0 ? 0ull : ((1ull << (t1 - d0)) - 1ull);
+    return w;
+}
+
+__global__ __launch_bounds__(256) void zstats_finalize_kernel(const double* mu, const double* sd,
+                                                              int K, int64_t lda, double* zs,
+                                                              int32_t* asset_ok) {
+    const int64_t a = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (a >= lda) return;
+    asset_ok[a] = zstats_asset(mu, sd, K, lda, a, zs);
 }
 
 __global__ __launch_bounds__(256) void row_bits_kernel(int64_t nch, int64_t lda, const uint64_t* a,
@@ -659,10 +754,32 @@ __global__ __launch_bounds__(256) void row_bits_kernel(int64_t nch, int64_t lda,
     u64 w = a[i];
     if (b) w &= b[i];
     if (asset_ok && !asset_ok[as]) w = 0;
-    const int64_t d0 = c << 6;
-    if (t0 > d0) w &= t0 - d0 >= 64 ? 0ull : (~0ull << (t0 - d0));
-    if (t1 - d0 < 64) w &= t1 <= d0 ? 0ull : ((1ull << (t1 - d0)) - 1ull);
-    out[i] = w;
+    out[i] = date_range_word(w, c, t0, t1);
+}
+
+// zstats_finalize_kernel and the row_bits_kernel that follows it in ONE launch.  A workgroup owns
+// 64 assets; its four waves share an asset's features (k = wave, wave + 4, ..), AND their flags
+// through LDS, then share its nch words out[c][a] = rows[c][a] (0 for a dropped asset)
+// restricted to the dates [t0, t1): both parts are chains of dependent-latency loads per asset,
+// four times shorter this way.
+__global__ __launch_bounds__(256) void zstats_rows_kernel(const double* mu, const double* sd, int K,
+                                                          int64_t lda, double* zs,
+                                                          int32_t* asset_ok, int64_t nch,
+                                                          const uint64_t* __restrict__ rows,
+                                                          int64_t t0, int64_t t1,
+                                                          uint64_t* __restrict__ out) {
+    __shared__ int sok[4][64];
+    const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const int64_t a = (int64_t)blockIdx.x * 64 + lane;
+    const bool live = a < lda;
+    sok[q][lane] = live ? zstats_asset(mu, sd, K, lda, a, zs, q, 4) : 0;
+    __syncthreads();
+    if (!live) return;
+    const int ok = sok[0][lane] & sok[1][lane] & sok[2][lane] & sok[3][lane];
+    if (q == 0) asset_ok[a] = ok;
+#pragma unroll 4
+    for (int64_t c = q; c < nch; c += 4)
+        out[c * lda + a] = date_range_word(ok ? rows[c * lda + a] : 0ull, c, t0, t1);
 }
 
 // pred[t][a] = b0 + sum_j b_j z_j, j ascending, zero coefficients skipped; NaN where the row bit
@@ -719,9 +836,6 @@ __global__ __launch_bounds__(256) void zpredict_kernel(const double* base, int64
 }  // namespace afm
 
 using namespace afm;
-
-// tile shape of a p-regressor design: 2 tiles (p + 2 <= 32) or 7 (p + 2 <= 108)
-static int zgram_nt(int p) { return p + 2 <= 32 ? 2 : 7; }
 
 extern "C" int afm_zgram_part_bytes(int p) {
     return (int)sizeof(double) * (zgram_nt(p) == 2 ? ZCfg<2>::PE : ZCfg<7>::PE);
@@ -807,6 +921,60 @@ extern "C" int afm_gram_tree_f64(afm_ctx* ctx, int p, const double* in, int64_t 
     else
         hipLaunchKernelGGL(tree_merge_kernel<7>, dim3(ng, 4), dim3(256), 0, ctx->stream, in, total,
                            per, final_out, p + 2, out);
+    AFM_HIP(hipGetLastError());
+    return AFM_OK;
+}
+
+extern "C" int afm_gram_tree3_f64(afm_ctx* ctx, int p, const double* leaves, int nrb, int c1,
+                                  int c2, int rb_per_blk, int nblk, double* out) {
+    AFM_CTX(ctx);
+    AFM_CHECK_ARG(leaves && out, "null buffer");
+    AFM_CHECK_ARG(p >= 1 && p + 2 <= ZCfg<7>::KMAX, "need 1 <= p <= 106");
+    AFM_CHECK_ARG(nrb >= 0 && nblk >= 0, "bad leaf counts");
+    AFM_CHECK_ARG(c1 >= 1 && c1 <= 32 && c2 >= 1 && c2 <= 32 && rb_per_blk >= 1 &&
+                      rb_per_blk <= 32 && c2 * rb_per_blk <= kT3Items,
+                  "need 1 <= c1, c2, rb_per_blk <= 32 and c2 * rb_per_blk <= 64");
+    AFM_CHECK_ARG((int64_t)nblk * rb_per_blk >= nrb, "nblk blocks do not hold nrb row-blocks");
+    if (nblk == 0) return AFM_OK;
+    if (zgram_nt(p) == 2)
+        hipLaunchKernelGGL(tree3_kernel<2>, dim3(ZCfg<2>::PE / 64, (unsigned)nblk),
+                           dim3(kT3Waves * 64), 0, ctx->stream, leaves, nrb, c1, c2, rb_per_blk,
+                           out);
+    else
+        hipLaunchKernelGGL(tree3_kernel<7>, dim3(ZCfg<7>::PE / 64, (unsigned)nblk),
+                           dim3(kT3Waves * 64), 0, ctx->stream, leaves, nrb, c1, c2, rb_per_blk,
+                           out);
+    AFM_HIP(hipGetLastError());
+    return AFM_OK;
+}
+
+extern "C" int afm_gram_final_f64(afm_ctx* ctx, int p, const double* blocks, int nblk,
+                                  const double* te_leaves, int nte, double* gram,
+                                  double* te_gram) {
+    AFM_CTX(ctx);
+    AFM_CHECK_ARG(blocks && gram, "null buffer");
+    AFM_CHECK_ARG(p >= 1 && p + 2 <= ZCfg<7>::KMAX, "need 1 <= p <= 106");
+    AFM_CHECK_ARG(nblk >= 1 && nblk <= 32, "need 1 <= nblk <= 32");
+    AFM_CHECK_ARG(!te_leaves || (te_gram && nte >= 1 && nte <= 32),
+                  "te_leaves need te_gram and 1 <= nte <= 32");
+    if (zgram_nt(p) == 2)
+        hipLaunchKernelGGL(gram_final_kernel<2>, dim3(ZCfg<2>::PE / 256), dim3(256), 0,
+                           ctx->stream, blocks, nblk, te_leaves, nte, p + 2, gram, te_gram);
+    else
+        hipLaunchKernelGGL(gram_final_kernel<7>, dim3(ZCfg<7>::PE / 256), dim3(256), 0,
+                           ctx->stream, blocks, nblk, te_leaves, nte, p + 2, gram, te_gram);
+    AFM_HIP(hipGetLastError());
+    return AFM_OK;
+}
+
+extern "C" int afm_zstats_rows_f64(afm_ctx* ctx, const double* mu, const double* sd, int K,
+                                   int64_t lda, double* zs, int32_t* asset_ok, int64_t nch,
+                                   const uint64_t* rows, int64_t t0, int64_t t1, uint64_t* out) {
+    AFM_CTX(ctx);
+    AFM_CHECK_ARG(mu && sd && zs && asset_ok && rows && out, "null buffer");
+    AFM_CHECK_ARG(K >= 1 && lda > 0 && nch >= 0, "bad shape");
+    hipLaunchKernelGGL(zstats_rows_kernel, dim3((unsigned)((lda + 63) / 64)), dim3(256), 0,
+                       ctx->stream, mu, sd, K, lda, zs, asset_ok, nch, rows, t0, t1, out);
     AFM_HIP(hipGetLastError());
     return AFM_OK;
 }
