@@ -1039,7 +1039,7 @@ class Pipeline:
                 "beta": refit.cpu().numpy()}
 
     def factor_screen(self, split: str = "train", z: bool = True, columns=None,
-                      corr_method: str = "pearson") -> dict:
+                      corr_method: str = "pearson", layers: bool = False) -> dict:
         """Factor screening on the last ``step()``'s resident panel (one GPU): the per-date IC
         (``corr_method``: 'pearson', or 'spearman' for the rank IC) of every column against
         return_1 / 2 / 5, its per-year IR and whole-sample
@@ -1056,8 +1056,11 @@ class Pipeline:
         Runs on the caller's stream in buffers of its own (allocated on first use).  Returns host
         arrays ``ic`` [nd][K][3], ``stats`` [K][3][5] (n, mean, std, IR, t), ``ir_year``
         [nyears][K][3], ``nrows`` [T], ``dates_idx`` (calendar indices of the evaluated dates),
-        ``years``, ``year0`` and the names ``features``.  No layers or top-k per factor, and not
-        the multi-GPU pipeline."""
+        ``years``, ``year0`` and the names ``features``.  ``layers=True``: also the decile layered
+        returns, long-short spreads and top-10 backtest of every column on the same rows and dates
+        (KKT:324-375) -- ``layer_mean`` [nd][K][3][10], ``layer_cnt`` [nd][K][10], ``port``
+        [nd][K][3], ``cum_layer`` [nd][K][3][10], ``ls`` [nd][K][3][5], ``cum_port`` [nd][K][3],
+        ``screen_grid``'s.  Not the multi-GPU pipeline."""
         import torch
         from .analyzer import check_corr_method
         from .screen import screen_grid
@@ -1094,8 +1097,11 @@ class Pipeline:
             r = screen_grid(self.out[0, a0:t1], cols, self.full.close[a0:t1],
                             b["price_bits"][w0:w1], b["row_bits"][w0:w1], A=self.A,
                             zs=self.zs if z else None, zcols=zcols, col_stride=T * lda,
-                            year=years[a0:t1], bufs=b, corr_method=corr_method)
-            out = {k: r[k].cpu().numpy() for k in ("ic", "stats", "ir_year")}
+                            year=years[a0:t1], bufs=b, corr_method=corr_method,
+                            layers=layers)
+            keys = ("ic", "stats", "ir_year") + (("layer_mean", "layer_cnt", "port", "cum_layer",
+                                                  "ls", "cum_port") if layers else ())
+            out = {k: r[k].cpu().numpy() for k in keys}
             nrows = np.zeros(T, dtype=np.int32)
             nrows[a0:t1] = r["nrows"].cpu().numpy()
         out.update(nrows=nrows, dates_idx=r["dates_idx"] + np.int32(a0), years=r["years"],

@@ -7,9 +7,13 @@ and the per-date demeans (KKT:308-320), so ``screen_grid`` prepares those once a
 IC of every column per date (KKT:342-349) -- Pearson, or with ``corr_method='spearman'`` the rank
 IC (the reference's ``corr_method`` attribute, KKT:286) -- its per-year IR (KKT:351-354) and a
 whole-sample summary (csrc/screen.hip, csrc/rankic.hip, include/afm_screen.h,
-include/afm_rankic.h).  ``FactorScreen`` is the frame interface beside ``AlphaSignalAnalyzer``.
+include/afm_rankic.h).  With ``layers=True`` the same pass also gives the other half of the
+reference's single-factor evaluation for every column: the decile layered returns, the long-short
+spreads and the factor-weighted top-10 backtest (KKT:324-375; csrc/screen_layers.hip,
+include/afm_screen_layers.h).  ``FactorScreen`` is the frame interface beside
+``AlphaSignalAnalyzer``.
 
-Out of scope: the decile layers and the top-k backtest per factor, and the multi-GPU pipeline.
+Out of scope: the multi-GPU pipeline.
 """
 from __future__ import annotations
 
@@ -24,7 +28,7 @@ STATS = ["n", "mean", "std", "IR", "t"]
 
 def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zcols=None,
                 col_stride=None, dates_idx=None, year=None, bufs=None,
-                corr_method="pearson") -> dict:
+                corr_method="pearson", layers=False) -> dict:
     """Device-level screen on grids.  ``base``: the panel, plane k of the screen at ``base +
     cols[k] * col_stride`` ([T][lda] each; ``col_stride`` defaults to T * lda); ``close`` [T][lda]
     with ``price_bits`` presence (the price rows of the forward returns); ``row_bits``: the row
@@ -36,8 +40,15 @@ def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zco
     elsewhere (the shared merge / dropna cascade and demeans; A <= 32768 as there), then the IC
     of every (date, column, return) and the summary.  ``dates_idx``: the evaluated dates (default:
     those with rows); ``year`` [T]: calendar years for the per-year IR.  ``corr_method``: 'pearson'
-    or 'spearman' (the rank IC: the return ranks of a date are taken once for all columns).  No
-    layers or top-k (use ``evaluate_grid`` on the columns that pass the screen).
+    or 'spearman' (the rank IC: the return ranks of a date are taken once for all columns).
+
+    ``layers=True``: also the backtests of every column on the same preparation and dates, whatever
+    ``corr_method`` is -- ``layer_mean`` [nd][K][3][10], ``layer_cnt`` [nd][K][10] (int32),
+    ``port`` [nd][K][3], ``cum_layer`` [nd][K][3][10], ``ls`` [nd][K][3][5] and ``cum_port``
+    [nd][K][3]: for a column without NaN on the rows what ``evaluate_grid`` gives for it alone,
+    bit for bit.  A NaN cell has no rank and is left out for its own column; +-inf cells are
+    ranked (pandas ``rank``), unlike in the IC.  The returns stay those demeaned over the shared
+    rows.
 
     Returns device tensors ``ic`` [nd][K][3], ``stats`` [K][3][5] (n, mean, std, IR, t over the
     non-NaN ICs), ``ir_year`` [nyears][K][3], ``nrows``, ``rows_idx``, and the host arrays
@@ -95,12 +106,57 @@ def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zco
     sscr = _buffer(bufs, "summary_scratch", (K, 3, 2, max(nd, 1)), f64, dev)
     call("afm_screen_summary_f64", ic if nd else sscr, nd, K, y_t, ny, y0, stats,
          ir_year if ny else sscr, sscr)
-    return {"ic": ic, "stats": stats, "ir_year": ir_year, "nrows": nrows, "rows_idx": rows_idx,
-            "dates_idx": dates_idx, "years": yr, "year0": y0}
+    out = {"ic": ic, "stats": stats, "ir_year": ir_year, "nrows": nrows, "rows_idx": rows_idx,
+           "dates_idx": dates_idx, "years": yr, "year0": y0}
+    if layers:
+        lm = _buffer(bufs, "layer_mean", (nd, K, 3, 10), f64, dev)
+        lc = _buffer(bufs, "layer_cnt", (nd, K, 10), i32, dev)
+        port = _buffer(bufs, "port", (nd, K, 3), f64, dev)
+        cum_layer = _buffer(bufs, "cum_layer", (nd, K, 3, 10), f64, dev)
+        ls = _buffer(bufs, "ls", (nd, K, 3, 5), f64, dev)
+        cum_port = _buffer(bufs, "cum_port", (nd, K, 3), f64, dev)
+        if nd:
+            lscr = _buffer(bufs, "layers_scratch", (nd * K * 40 + K,), f64, dev)
+            call("afm_screen_layers_f64", base, col_stride, T, lda, cols_t, K, zs, zc_t, d_t, nd,
+                 rows, rows_idx, nrows, lm, lc, port, lscr)
+            call("afm_screen_layer_series_f64", nd, K, lm, port, cum_layer, ls, cum_port)
+        out.update(layer_mean=lm, layer_cnt=lc, port=port, cum_layer=cum_layer, ls=ls,
+                   cum_port=cum_port)
+    return out
+
+
+LAYER_STATS = ["top_minus_bottom", "monotonic", "top_k"]
+
+
+def _last_valid(x):
+    """x [nd][...] -> [...]: the last non-NaN entry along the dates (NaN where there is none)."""
+    ok = ~np.isnan(x)
+    if x.shape[0] == 0:
+        return np.full(x.shape[1:], np.nan)
+    idx = x.shape[0] - 1 - np.argmax(ok[::-1], axis=0)
+    v = np.take_along_axis(x, idx[None], axis=0)[0]
+    return np.where(ok.any(axis=0), v, np.nan)
+
+
+def _layer_spearman(final):
+    """final [N][10] (NaN: layer absent) -> [N]: the Spearman correlation of the layer number with
+    the value over the layers present (average ranks; NaN under two layers or without spread)."""
+    import pandas as pd
+    have = ~np.isnan(final)
+    num = np.where(have, np.arange(1.0, 11.0), np.nan)
+    rx = pd.DataFrame(num).rank(axis=1).to_numpy()
+    ry = pd.DataFrame(final).rank(axis=1).to_numpy()
+    with np.errstate(all="ignore"):
+        n = have.sum(axis=1)
+        dx = np.where(have, rx - np.nansum(rx, axis=1, keepdims=True) / n[:, None], 0.0)
+        dy = np.where(have, ry - np.nansum(ry, axis=1, keepdims=True) / n[:, None], 0.0)
+        den = np.sqrt((dx * dx).sum(axis=1) * (dy * dy).sum(axis=1))
+        return np.where((n >= 2) & (den > 0), (dx * dy).sum(axis=1) / den, np.nan)
 
 
 class FactorScreen:
-    """``FactorScreen(factors_df, price_data, columns=None, corr_method="pearson").run()``: the
+    """``FactorScreen(factors_df, price_data, columns=None, corr_method="pearson",
+    layers=False).run()``: the
     IC / IR screen (Pearson, or with 'spearman' the rank IC, as the analyzer's ``corr_method``) of
     every column of ``factors_df`` -- indexed (date, id), one column per factor, e.g. the reference's
     ``df_train_x`` -- against the forward returns of ``price_data`` (what ``AlphaSignalAnalyzer``
@@ -110,11 +166,25 @@ class FactorScreen:
 
     After ``run()``: ``ic_df`` (date, factor, Type, IC; NaN ICs dropped; ordered by date, factor
     in column order, Type), ``ir_df`` (year, factor, Type, IR) and ``summary`` (factor, Type, n,
-    mean, std, IR, t; by \\|IR\\| descending, ties in column order, NaN last).  Layers and the
-    top-k backtest are the analyzer's."""
+    mean, std, IR, t; by \\|IR\\| descending, ties in column order, NaN last).
 
-    def __init__(self, factors_df, price_data, columns=None, corr_method="pearson"):
+    ``layers=True`` adds the analyzer's backtest frames for every column, with a ``factor`` column
+    after ``date`` and ordered by date, then factor in column order: ``layered_ret_dfs[rt]``
+    (date, factor, layer, rt: the cumulative layer returns, the layers the factor has on any date,
+    NaN entries dropped), ``ls_ret_dfs[rt]`` (date, factor, layer, rt: the long-short spreads,
+    layer 5 = 10 minus 1 first) and ``port_ret_df`` (date, factor, Type, Returns: the top-10
+    returns and their cumulative sums) -- for a column without NaN the rows of
+    ``AlphaSignalAnalyzer``'s frames; a NaN cell is left out of its own column's ranks, an inf
+    cell is ranked.  And ``layer_summary``: one row per (factor, Type) with ``top_minus_bottom``
+    (the last non-NaN cumulative layer 10 minus layer 1), ``monotonic`` (the Spearman correlation
+    of the layer number with the final cumulative layer return over the layers present) and
+    ``top_k`` (the final cumulative top-10 return), by \\|top_minus_bottom\\| descending as
+    ``summary``."""
+
+    def __init__(self, factors_df, price_data, columns=None, corr_method="pearson",
+                 layers=False):
         self.corr_method = check_corr_method(corr_method)
+        self.layers = bool(layers)
         self.factors_df = factors_df
         self.columns = list(columns) if columns is not None else list(factors_df.columns)
         self.return_type = list(RETURN_TYPES)
@@ -152,7 +222,7 @@ class FactorScreen:
         pm[pt, pa] = True
         year = dates.astype("datetime64[Y]").astype(np.int64) + 1970
         r = screen_grid(base, np.arange(K), close, pack_bits(pm), pack_bits(rm), A=A, year=year,
-                        corr_method=self.corr_method)
+                        corr_method=self.corr_method, layers=self.layers)
         r["dates"], r["ids"] = dates, ids
         self._res = r
         ic = r["ic"].cpu().numpy()                                   # [nd][K][3]
@@ -186,4 +256,47 @@ class FactorScreen:
         summary.insert(0, "Type", np.tile(types, K))
         summary.insert(0, "factor", np.repeat(names, 3))
         self.summary = summary.iloc[order].reset_index(drop=True)
+        if self.layers:
+            self._layer_frames(dts, names, types)
         return self
+
+    def _layer_frames(self, dts, names, types):
+        """The analyzer's _calc_layered_ret / _backtest_top_stocks frames (afm/analyzer.py) for
+        every column at once."""
+        import pandas as pd
+        r = self._res
+        nd, K = len(dts), len(names)
+        cum = r["cum_layer"].cpu().numpy()                           # [nd][K][3][10]
+        ls = r["ls"].cpu().numpy()                                   # [nd][K][3][5]
+        port, cum_port = r["port"].cpu().numpy(), r["cum_port"].cpu().numpy()
+        present = (r["layer_cnt"].cpu().numpy() > 0).any(axis=0)     # [K][10]: the factor's layers
+        self.layered_ret_dfs, self.ls_ret_dfs = {}, {}
+        for q, rt in enumerate(types):
+            v = cum[:, :, q, :]
+            keep = (present[None] & ~np.isnan(v)).reshape(-1)
+            self.layered_ret_dfs[rt] = pd.DataFrame({
+                "date": np.repeat(dts.values, K * 10)[keep],
+                "factor": np.tile(np.repeat(names, 10), nd)[keep],
+                "layer": np.tile(np.arange(1, 11, dtype=np.int64), nd * K)[keep],
+                rt: v.reshape(-1)[keep]})
+            v = ls[:, :, q, :]
+            keep = ~np.isnan(v.reshape(-1))
+            self.ls_ret_dfs[rt] = pd.DataFrame({
+                "date": np.repeat(dts.values, K * 5)[keep],
+                "factor": np.tile(np.repeat(names, 5), nd)[keep],
+                "layer": np.tile(np.arange(5, 0, -1, dtype=np.int64), nd * K)[keep],
+                rt: v.reshape(-1)[keep]})
+        tnames = np.asarray(list(types) + [f"cum_{x}" for x in types], dtype=object)
+        self.port_ret_df = pd.DataFrame({
+            "date": np.repeat(dts.values, K * 6),
+            "factor": np.tile(np.repeat(names, 6), nd),
+            "Type": np.tile(tnames, nd * K),
+            "Returns": np.concatenate([port, cum_port], axis=2).reshape(-1)})
+        tmb = _last_valid(ls[:, :, :, 0]).reshape(-1)                # cum[10] - cum[1]
+        mono = _layer_spearman(_last_valid(cum).reshape(K * 3, 10))
+        topk = _last_valid(cum_port).reshape(-1)
+        key = np.abs(tmb)
+        order = np.argsort(np.where(np.isnan(key), -np.inf, key) * -1.0, kind="stable")
+        ly = pd.DataFrame({"factor": np.repeat(names, 3), "Type": np.tile(types, K),
+                           "top_minus_bottom": tmb, "monotonic": mono, "top_k": topk})
+        self.layer_summary = ly.iloc[order].reset_index(drop=True)

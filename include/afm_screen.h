@@ -9,8 +9,8 @@
  * columns of one frame share the rows, the forward returns and the per-date demeans, so those
  * are prepared once (afm_fwd_returns_f64, afm_xs_prepare_f64 with a signal plane that marks the
  * rows) and these two entry points evaluate every column on them.  The rank (Spearman) IC of the
- * same columns is afm_rankic.h's; decile layers and the top-k backtest per factor are out of
- * scope.
+ * same columns is afm_rankic.h's; the decile layers, long-short spreads and top-10 backtest of
+ * every column on the same preparation (KKT:324-375) are afm_screen_layers.h's.
  */
 #ifndef AFM_SCREEN_H
 #define AFM_SCREEN_H
