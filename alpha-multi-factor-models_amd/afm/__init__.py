@@ -23,11 +23,11 @@ from . import regression  # noqa: F401
 from .regression import (Lasso, LassoCV, LinearRegression, cross_sectional_ols,  # noqa: F401
                          lasso_path)
 from .analyzer import AlphaSignalAnalyzer  # noqa: F401
-from .screen import FactorScreen, screen_grid  # noqa: F401
+from .screen import FactorScreen, screen_grid, select_factors  # noqa: F401
 from .portfolio import PortfolioManager, mean_variance_weights  # noqa: F401
 from .zscore import split_zscore, zscore_grid  # noqa: F401
 
 __all__ = ["compute_factors", "factor_panel", "FACTOR_NAMES", "PanelGrid", "pack_bits",
            "unpack_bits", "LinearRegression", "Lasso", "LassoCV", "lasso_path",
            "cross_sectional_ols", "AlphaSignalAnalyzer", "FactorScreen", "screen_grid",
-           "PortfolioManager", "split_zscore", "zscore_grid"]
+           "select_factors", "PortfolioManager", "split_zscore", "zscore_grid"]

@@ -1,5 +1,6 @@
 """ctypes binding of libafm.so (the C-ABI declared in include/afm.h, include/afm_mv.h,
-include/afm_screen.h, include/afm_rankic.h, include/afm_seams.h and include/afm_screen_layers.h).
+include/afm_screen.h, include/afm_rankic.h, include/afm_seams.h, include/afm_screen_layers.h and
+include/afm_xcorr.h).
 
 The product path has no CPU fallback: if the library is missing or no GPU is visible, every
 call raises.  ``make -C alpha-multi-factor-models_amd`` (or ``__graft_entry__.build()``) builds
@@ -139,7 +140,14 @@ SIGNATURES_LAYERS = {
                                         "i32* f64* i32* f64* f64*"),
     "afm_screen_layer_series_f64": ("status", "ctx i64 int f64* f64* f64* f64* f64*"),
 }
-BOUND_TABLES = LOADED_TABLES + (SIGNATURES_LAYERS,)   # what lib() declares and Context.call resolves
+BOUND_TABLES = LOADED_TABLES + (SIGNATURES_LAYERS,)
+# ... and for include/afm_xcorr.h, the cross-factor correlation of the screen (tests/test_abi_xcorr.py)
+SIGNATURES_XCORR = {
+    "afm_screen_xcorr_f64": ("status", "ctx f64* i64 i64 i64 i32* int f64* i32* i32* i64 f64* i32* "
+                                       "i32* f64*"),
+    "afm_screen_xcorr_summary_f64": ("status", "ctx f64* i64 int f64*"),
+}
+CALL_TABLES = BOUND_TABLES + (SIGNATURES_XCORR,)   # what lib() declares and Context.call resolves
 _RESTYPE = {"status": I32, "int": I32, "i64": I64, "str": ctypes.c_char_p}
 _ARGTYPE = {"int": I32, "i64": I64, "f64": DBL, "str": ctypes.c_char_p}    # every pointer: void*
 
@@ -161,7 +169,7 @@ def lib():
                     raise ImportError(f"{LIB_PATH} is not built: run `make -C "
                                       f"{os.path.dirname(HERE)}` (hipcc, gfx950)")
                 L = ctypes.CDLL(LIB_PATH)
-                for table in BOUND_TABLES:
+                for table in CALL_TABLES:
                     for name, (res, params) in table.items():
                         f = getattr(L, name)
                         f.restype = _RESTYPE[res]
@@ -207,7 +215,7 @@ def _plans(device: int) -> dict:
     negative = (0).__gt__
     failed = {"status": bool, "int": negative, "i64": negative, "str": lambda s: s is None}
     plans = {}
-    for name, (res, params) in (item for table in BOUND_TABLES for item in table.items()):
+    for name, (res, params) in (item for table in CALL_TABLES for item in table.items()):
         toks = params.split()
         takes_ctx = toks[:1] == ["ctx"]
         convs = tuple(_device_buffer(buffer[t], device, f"{name} argument {i}") if t in buffer

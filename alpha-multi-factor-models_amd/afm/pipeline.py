@@ -1039,7 +1039,8 @@ class Pipeline:
                 "beta": refit.cpu().numpy()}
 
     def factor_screen(self, split: str = "train", z: bool = True, columns=None,
-                      corr_method: str = "pearson", layers: bool = False) -> dict:
+                      corr_method: str = "pearson", layers: bool = False,
+                      xcorr: bool = False) -> dict:
         """Factor screening on the last ``step()``'s resident panel (one GPU): the per-date IC
         (``corr_method``: 'pearson', or 'spearman' for the rank IC) of every column against
         return_1 / 2 / 5, its per-year IR and whole-sample
@@ -1060,7 +1061,20 @@ class Pipeline:
         returns, long-short spreads and top-10 backtest of every column on the same rows and dates
         (KKT:324-375) -- ``layer_mean`` [nd][K][3][10], ``layer_cnt`` [nd][K][10], ``port``
         [nd][K][3], ``cum_layer`` [nd][K][3][10], ``ls`` [nd][K][3][5], ``cum_port`` [nd][K][3],
-        ``screen_grid``'s.  Not the multi-GPU pipeline."""
+        ``screen_grid``'s.
+
+        ``xcorr=True``: also how the columns relate to each other (always Pearson) --
+        ``xcorr_stats`` [K][K][3] = (n, mean r, mean \|r\|) over the dates of the per-date
+        correlation matrix of the columns on the same rows, a host array; the per-date matrices
+        ``xcorr_dev`` [nd][K][K] stay on the device (hundreds of MB at full size; the buffer is
+        reused by the next call).  The intended loop -- screen, prune what is redundant, refit::
+
+            r = pipe.factor_screen("train", xcorr=True)
+            sel = select_factors(r["features"], r["stats"][:, 0, 3], r["xcorr_stats"][:, :, 2],
+                                 max_corr=0.7, k=30)
+            pipe2 = Pipeline(panel, PipelineConfig(fm_features=tuple(sel)))
+
+        Not the multi-GPU pipeline."""
         import torch
         from .analyzer import check_corr_method
         from .screen import screen_grid
@@ -1098,10 +1112,14 @@ class Pipeline:
                             b["price_bits"][w0:w1], b["row_bits"][w0:w1], A=self.A,
                             zs=self.zs if z else None, zcols=zcols, col_stride=T * lda,
                             year=years[a0:t1], bufs=b, corr_method=corr_method,
-                            layers=layers)
+                            layers=layers, xcorr=xcorr)
             keys = ("ic", "stats", "ir_year") + (("layer_mean", "layer_cnt", "port", "cum_layer",
                                                   "ls", "cum_port") if layers else ())
+            if xcorr:
+                keys += ("xcorr_stats",)
             out = {k: r[k].cpu().numpy() for k in keys}
+            if xcorr:
+                out["xcorr_dev"] = r["xcorr"]
             nrows = np.zeros(T, dtype=np.int32)
             nrows[a0:t1] = r["nrows"].cpu().numpy()
         out.update(nrows=nrows, dates_idx=r["dates_idx"] + np.int32(a0), years=r["years"],

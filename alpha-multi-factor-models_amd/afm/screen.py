@@ -10,8 +10,11 @@ whole-sample summary (csrc/screen.hip, csrc/rankic.hip, include/afm_screen.h,
 include/afm_rankic.h).  With ``layers=True`` the same pass also gives the other half of the
 reference's single-factor evaluation for every column: the decile layered returns, the long-short
 spreads and the factor-weighted top-10 backtest (KKT:324-375; csrc/screen_layers.hip,
-include/afm_screen_layers.h).  ``FactorScreen`` is the frame interface beside
-``AlphaSignalAnalyzer``.
+include/afm_screen_layers.h).  With ``xcorr=True`` it gives what the reference never looks at: how the
+columns relate to each other -- the per-date correlation matrix of the screened columns, its mean
+over the dates, and ``select_factors``, a greedy "best IR first, drop what is too correlated with
+what is kept" choice of columns (csrc/xcorr.hip, include/afm_xcorr.h).  ``FactorScreen`` is the
+frame interface beside ``AlphaSignalAnalyzer``.
 
 Out of scope: the multi-GPU pipeline.
 """
@@ -28,7 +31,7 @@ STATS = ["n", "mean", "std", "IR", "t"]
 
 def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zcols=None,
                 col_stride=None, dates_idx=None, year=None, bufs=None,
-                corr_method="pearson", layers=False) -> dict:
+                corr_method="pearson", layers=False, xcorr=False) -> dict:
     """Device-level screen on grids.  ``base``: the panel, plane k of the screen at ``base +
     cols[k] * col_stride`` ([T][lda] each; ``col_stride`` defaults to T * lda); ``close`` [T][lda]
     with ``price_bits`` presence (the price rows of the forward returns); ``row_bits``: the row
@@ -49,6 +52,13 @@ def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zco
     bit for bit.  A NaN cell has no rank and is left out for its own column; +-inf cells are
     ranked (pandas ``rank``), unlike in the IC.  The returns stay those demeaned over the shared
     rows.
+
+    ``xcorr=True``: also ``xcorr`` [nd][K][K], the correlation matrix of the K columns on each
+    evaluated date over the shared rows (``DataFrame.corr()``: pairwise complete, a non-finite
+    cell missing for its own column, NaN under two joint rows or without variance, the diagonal
+    exactly 1.0 or NaN), and ``xcorr_stats`` [K][K][3] = (n, mean r, mean \|r\|) of every pair
+    over the dates.  On the same preparation and dates as the IC, whatever ``corr_method`` is: the
+    factor-to-factor correlation is always Pearson (a Spearman variant is out of scope).
 
     Returns device tensors ``ic`` [nd][K][3], ``stats`` [K][3][5] (n, mean, std, IR, t over the
     non-NaN ICs), ``ir_year`` [nyears][K][3], ``nrows``, ``rows_idx``, and the host arrays
@@ -122,7 +132,41 @@ def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zco
             call("afm_screen_layer_series_f64", nd, K, lm, port, cum_layer, ls, cum_port)
         out.update(layer_mean=lm, layer_cnt=lc, port=port, cum_layer=cum_layer, ls=ls,
                    cum_port=cum_port)
+    if xcorr:
+        xc = _buffer(bufs, "xcorr", (nd, K, K), f64, dev)
+        xs = _buffer(bufs, "xcorr_stats", (K, K, 3), f64, dev)
+        if nd:
+            call("afm_screen_xcorr_f64", base, col_stride, T, lda, cols_t, K, zs, zc_t, d_t, nd,
+                 None, rows_idx, nrows, xc)
+        call("afm_screen_xcorr_summary_f64", xc if nd else None, nd, K, xs)
+        out.update(xcorr=xc, xcorr_stats=xs)
     return out
+
+
+def select_factors(names, score, corr_abs, max_corr=0.7, k=None) -> list:
+    """Greedy redundancy pruning: walk ``names`` by \|``score``\| descending (stable in the given
+    order; a NaN score leaves its name out) and keep a candidate when its ``corr_abs`` with every
+    name kept so far is <= ``max_corr`` (a NaN correlation counts as 0); stop at ``k`` names.
+    ``score`` [K]: e.g. the whole-sample IR of each name; ``corr_abs`` [K][K]: e.g. the mean
+    \|correlation\| over the dates (``FactorScreen.factor_corr_abs``), rows and columns in the
+    order of ``names``.  Returns the kept names in the order taken."""
+    names = list(names)
+    score = np.abs(np.asarray(score, dtype=np.float64).reshape(-1))
+    c = np.asarray(corr_abs, dtype=np.float64)
+    if score.shape != (len(names),) or c.shape != (len(names), len(names)):
+        raise ValueError("select_factors: score [K] and corr_abs [K][K] must match names")
+    if k is not None and k < 0:
+        raise ValueError("select_factors: k must not be negative")
+    c = np.where(np.isnan(c), 0.0, c)
+    order = [i for i in np.argsort(-np.where(np.isnan(score), 0.0, score), kind="stable")
+             if not np.isnan(score[i])]
+    kept = []
+    for i in order:
+        if k is not None and len(kept) >= k:
+            break
+        if all(c[i, j] <= max_corr for j in kept):
+            kept.append(int(i))
+    return [names[i] for i in kept]
 
 
 LAYER_STATS = ["top_minus_bottom", "monotonic", "top_k"]
@@ -179,12 +223,20 @@ class FactorScreen:
     (the last non-NaN cumulative layer 10 minus layer 1), ``monotonic`` (the Spearman correlation
     of the layer number with the final cumulative layer return over the layers present) and
     ``top_k`` (the final cumulative top-10 return), by \\|top_minus_bottom\\| descending as
-    ``summary``."""
+    ``summary``.
+
+    ``xcorr=True`` adds the relation of the columns to each other: ``factor_corr``,
+    ``factor_corr_abs`` and ``factor_corr_n`` (K x K frames, the factor names on both axes: the
+    mean and the mean absolute value over the dates of the per-date ``DataFrame.corr()`` of the
+    columns, and the number of dates that have it), ``redundant_pairs`` (factor_a, factor_b, mean,
+    mean_abs, n: one row per pair a before b with n > 0, by mean_abs descending, ties in column
+    order) and ``select(max_corr, k, return_type)``.  Always Pearson."""
 
     def __init__(self, factors_df, price_data, columns=None, corr_method="pearson",
-                 layers=False):
+                 layers=False, xcorr=False):
         self.corr_method = check_corr_method(corr_method)
         self.layers = bool(layers)
+        self.xcorr = bool(xcorr)
         self.factors_df = factors_df
         self.columns = list(columns) if columns is not None else list(factors_df.columns)
         self.return_type = list(RETURN_TYPES)
@@ -222,7 +274,7 @@ class FactorScreen:
         pm[pt, pa] = True
         year = dates.astype("datetime64[Y]").astype(np.int64) + 1970
         r = screen_grid(base, np.arange(K), close, pack_bits(pm), pack_bits(rm), A=A, year=year,
-                        corr_method=self.corr_method, layers=self.layers)
+                        corr_method=self.corr_method, layers=self.layers, xcorr=self.xcorr)
         r["dates"], r["ids"] = dates, ids
         self._res = r
         ic = r["ic"].cpu().numpy()                                   # [nd][K][3]
@@ -258,7 +310,35 @@ class FactorScreen:
         self.summary = summary.iloc[order].reset_index(drop=True)
         if self.layers:
             self._layer_frames(dts, names, types)
+        if self.xcorr:
+            self._xcorr_frames()
         return self
+
+    def _xcorr_frames(self):
+        import pandas as pd
+        xs = self._res["xcorr_stats"].cpu().numpy()                 # [K][K][3]
+        K, cols = len(self.columns), self.columns
+        self.factor_corr = pd.DataFrame(xs[:, :, 1], index=cols, columns=cols)
+        self.factor_corr_abs = pd.DataFrame(xs[:, :, 2], index=cols, columns=cols)
+        self.factor_corr_n = pd.DataFrame(xs[:, :, 0].astype(np.int64), index=cols, columns=cols)
+        ja, jb = np.triu_indices(K, 1)
+        have = xs[ja, jb, 0] > 0
+        ja, jb = ja[have], jb[have]
+        order = np.argsort(-xs[ja, jb, 2], kind="stable")
+        ja, jb = ja[order], jb[order]
+        names = np.asarray(cols, dtype=object)
+        self.redundant_pairs = pd.DataFrame({
+            "factor_a": names[ja], "factor_b": names[jb], "mean": xs[ja, jb, 1],
+            "mean_abs": xs[ja, jb, 2], "n": xs[ja, jb, 0].astype(np.int64)})
+
+    def select(self, max_corr=0.7, k=None, return_type="return_1") -> list:
+        """``select_factors`` on this screen: the columns by the \|whole-sample IR\| of
+        ``return_type``, pruned by ``factor_corr_abs``."""
+        if not self.xcorr or self._res is None:
+            raise ValueError("select(): needs FactorScreen(..., xcorr=True).run()")
+        q = self.return_type.index(return_type)
+        ir = self._res["stats"].cpu().numpy()[:, q, 3]
+        return select_factors(self.columns, ir, self.factor_corr_abs.to_numpy(), max_corr, k)
 
     def _layer_frames(self, dts, names, types):
         """The analyzer's _calc_layered_ret / _backtest_top_stocks frames (afm/analyzer.py) for

@@ -46,5 +46,39 @@ __device__ double seq_np_sum(const double* a, int64_t n) {      // np.add.reduce
     return r;
 }
 
+// The same sums of a sequence that is not contiguous in memory: element i is get(i0 + i) (a
+// strided view, a value mapped on the way).  Operation for operation leaf_sum / seq_pairwise /
+// seq_np_sum above.
+template <class Get>
+__device__ double leaf_sum_of(Get get, int64_t i0, int n) {
+    if (n < 8) {
+        double res = 0.;
+        for (int i = 0; i < n; ++i) res += get(i0 + i);
+        return res;
+    }
+    double r[8];
+    for (int j = 0; j < 8; ++j) r[j] = get(i0 + j);
+    int i;
+    for (i = 8; i < n - (n % 8); i += 8)
+        for (int j = 0; j < 8; ++j) r[j] += get(i0 + i + j);
+    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < n; ++i) res += get(i0 + i);
+    return res;
+}
+template <class Get>
+__device__ double seq_pairwise_of(Get get, int64_t i0, int64_t n) {
+    if (n <= 128) return leaf_sum_of(get, i0, (int)n);
+    int64_t n2 = n / 2;
+    n2 -= n2 % 8;
+    return seq_pairwise_of(get, i0, n2) + seq_pairwise_of(get, i0 + n2, n - n2);
+}
+template <class Get>
+__device__ double seq_np_sum_of(Get get, int64_t n) {
+    double r = 0.0;
+    for (int64_t c0 = 0; c0 < n; c0 += kNpBuf)
+        r = r + seq_pairwise_of(get, c0, n - c0 < kNpBuf ? n - c0 : kNpBuf);
+    return r;
+}
+
 }  // namespace
 }  // namespace afm
