@@ -11,6 +11,9 @@ Drop-in Python surface (same names, arguments and results as the reference):
                                                     (the choice of alpha KKT:605 hard-codes)
 * ``FactorScreen(df, prices).run()``               -- KKT:465, 472 for every column at once
                                                     (per-date IC, per-year IR, summary)
+* ``preprocess_factors(df, groups=..., prep=XsPrep(...))`` -- the per-date winsorise / sector-
+                                                    neutralise / standardise of every column
+                                                    (``groupby('date').transform``)
 * ``PortfolioManager(...)``                       -- KKT:795-970
 * ``split_zscore(all_df)``                       -- KKT:424-458 (z-score + split)
 
@@ -24,10 +27,12 @@ from .regression import (Lasso, LassoCV, LinearRegression, cross_sectional_ols, 
                          lasso_path)
 from .analyzer import AlphaSignalAnalyzer  # noqa: F401
 from .screen import FactorScreen, screen_grid, select_factors  # noqa: F401
+from .xsprep import XsPrep, preprocess_factors, preprocess_grid  # noqa: F401
 from .portfolio import PortfolioManager, mean_variance_weights  # noqa: F401
 from .zscore import split_zscore, zscore_grid  # noqa: F401
 
 __all__ = ["compute_factors", "factor_panel", "FACTOR_NAMES", "PanelGrid", "pack_bits",
            "unpack_bits", "LinearRegression", "Lasso", "LassoCV", "lasso_path",
            "cross_sectional_ols", "AlphaSignalAnalyzer", "FactorScreen", "screen_grid",
-           "select_factors", "PortfolioManager", "split_zscore", "zscore_grid"]
+           "select_factors", "PortfolioManager", "split_zscore", "zscore_grid", "XsPrep",
+           "preprocess_factors", "preprocess_grid"]

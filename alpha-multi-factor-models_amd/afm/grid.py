@@ -59,6 +59,7 @@ class PanelGrid:
     vbits: object              # torch [ceil(T/64)][lda] int64 (uint64 bit pattern)
     tradable: object = None    # torch [T][lda] bool
     tbits: object = None       # torch [ceil(T/64)][lda] present AND tradable bits
+    group: object = None       # [A] group (sector) label of each security (host), or None
 
     @property
     def T(self) -> int:
@@ -91,7 +92,8 @@ class PanelGrid:
         trad = up(p.tradable, torch.bool)
         return cls(dates=p.dates, ids=p.ids, close=up(p.close), volume=up(p.volume),
                    ret1d=up(p.ret1d), excess=up(p.excess), valid=valid, vbits=pack_bits(valid),
-                   tradable=trad, tbits=pack_bits(trad & valid))
+                   tradable=trad, tbits=pack_bits(trad & valid),
+                   group=None if p.group_id is None else np.asarray(p.group_id))
 
     @classmethod
     def from_frame(cls, df, device=None):
@@ -124,8 +126,18 @@ class PanelGrid:
         if "in_trading_universe" in df.columns:
             trad = torch.zeros((T, lda), dtype=torch.bool, device=dev)
             trad[ti, ai] = torch.from_numpy(df["in_trading_universe"].to_numpy() == "Y").to(dev)
+        group = None
+        if "group_id" in df.columns:       # one label per security, else no static grouping
+            lab = df["group_id"].to_numpy()
+            first = np.full(A, -1, dtype=np.int64)
+            first[a_idx[::-1]] = np.arange(len(df) - 1, -1, -1)        # first row of each id
+            same = lab == lab[first][a_idx]
+            if lab.dtype.kind == "f":
+                same |= np.isnan(lab) & np.isnan(lab[first][a_idx])
+            if bool(np.all(same)):
+                group = lab[first]
         g = cls(dates=np.asarray(dates, dtype="datetime64[ns]"), ids=ids.astype(np.int64),
                 close=plane("close_price"), volume=plane("volume"), ret1d=plane("ret1d"),
                 excess=plane("excess_ret1d"), valid=valid, vbits=pack_bits(valid), tradable=trad,
-                tbits=pack_bits(trad & valid) if trad is not None else None)
+                tbits=pack_bits(trad & valid) if trad is not None else None, group=group)
         return g, ti, ai

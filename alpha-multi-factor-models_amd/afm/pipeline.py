@@ -1040,7 +1040,7 @@ class Pipeline:
 
     def factor_screen(self, split: str = "train", z: bool = True, columns=None,
                       corr_method: str = "pearson", layers: bool = False,
-                      xcorr: bool = False) -> dict:
+                      xcorr: bool = False, prep=None, groups=None) -> dict:
         """Factor screening on the last ``step()``'s resident panel (one GPU): the per-date IC
         (``corr_method``: 'pearson', or 'spearman' for the rank IC) of every column against
         return_1 / 2 / 5, its per-year IR and whole-sample
@@ -1074,6 +1074,13 @@ class Pipeline:
                                  max_corr=0.7, k=30)
             pipe2 = Pipeline(panel, PipelineConfig(fm_features=tuple(sel)))
 
+        ``prep`` (an ``afm.xsprep.XsPrep``): every column is first winsorised / group-neutralised
+        / standardised across each evaluated date, over the split's rows of that date (with ``z``
+        the z values are what is preprocessed), and the screen reads the result
+        (``screen_grid(..., prep=...)``).  ``groups``: a host array [A] of group (sector) labels of
+        any dtype, one per security (default: the grid's ``group``; NaN: in no group).  The result
+        gains ``prep_info`` [nd][K][7] = (n, lo, hi, n_lo, n_hi, mean, std).
+
         Not the multi-GPU pipeline."""
         import torch
         from .analyzer import check_corr_method
@@ -1100,6 +1107,16 @@ class Pipeline:
             self._screen_bufs = {"row_bits": torch.zeros((nch, lda), **self._opts[1]),
                                  "price_bits": torch.zeros((nch, lda), **self._opts[1])}
         b = self._screen_bufs
+        gdev, G = None, 0
+        if prep is not None and prep.neutralize:
+            from .xsprep import factorize_groups
+            labels = groups if groups is not None else self.full.group
+            if labels is None or len(labels) != self.A:
+                raise ValueError("factor_screen(prep.neutralize): groups must hold one label per "
+                                 f"security ({self.A})")
+            codes, G = factorize_groups(labels)
+            gdev = torch.full((lda,), -1, dtype=torch.int32, device=dev)
+            gdev[:self.A] = torch.from_numpy(codes).to(dev)
         a0 = (t0 // 64) * 64                # the split's sub-grid, 64-date aligned (bit words)
         w0, w1 = a0 // 64, (t1 + 63) // 64
         years = np.asarray(self.full.dates).astype("datetime64[Y]").astype(np.int64) + 1970
@@ -1112,11 +1129,14 @@ class Pipeline:
                             b["price_bits"][w0:w1], b["row_bits"][w0:w1], A=self.A,
                             zs=self.zs if z else None, zcols=zcols, col_stride=T * lda,
                             year=years[a0:t1], bufs=b, corr_method=corr_method,
-                            layers=layers, xcorr=xcorr)
+                            layers=layers, xcorr=xcorr, prep=prep, groups=gdev,
+                            ngroups=max(G, 1))
             keys = ("ic", "stats", "ir_year") + (("layer_mean", "layer_cnt", "port", "cum_layer",
                                                   "ls", "cum_port") if layers else ())
             if xcorr:
                 keys += ("xcorr_stats",)
+            if prep is not None:
+                keys += ("prep_info",)
             out = {k: r[k].cpu().numpy() for k in keys}
             if xcorr:
                 out["xcorr_dev"] = r["xcorr"]

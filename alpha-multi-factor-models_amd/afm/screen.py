@@ -13,8 +13,10 @@ spreads and the factor-weighted top-10 backtest (KKT:324-375; csrc/screen_layers
 include/afm_screen_layers.h).  With ``xcorr=True`` it gives what the reference never looks at: how the
 columns relate to each other -- the per-date correlation matrix of the screened columns, its mean
 over the dates, and ``select_factors``, a greedy "best IR first, drop what is too correlated with
-what is kept" choice of columns (csrc/xcorr.hip, include/afm_xcorr.h).  ``FactorScreen`` is the
-frame interface beside ``AlphaSignalAnalyzer``.
+what is kept" choice of columns (csrc/xcorr.hip, include/afm_xcorr.h).  With ``prep=XsPrep(...)``
+every column is first winsorised, group-neutralised and standardised across each date
+(afm/xsprep.py, csrc/xsprep.hip, include/afm_xsprep.h) and all of the above rate the result.
+``FactorScreen`` is the frame interface beside ``AlphaSignalAnalyzer``.
 
 Out of scope: the multi-GPU pipeline.
 """
@@ -31,7 +33,8 @@ STATS = ["n", "mean", "std", "IR", "t"]
 
 def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zcols=None,
                 col_stride=None, dates_idx=None, year=None, bufs=None,
-                corr_method="pearson", layers=False, xcorr=False) -> dict:
+                corr_method="pearson", layers=False, xcorr=False, prep=None, groups=None,
+                ngroups=0) -> dict:
     """Device-level screen on grids.  ``base``: the panel, plane k of the screen at ``base +
     cols[k] * col_stride`` ([T][lda] each; ``col_stride`` defaults to T * lda); ``close`` [T][lda]
     with ``price_bits`` presence (the price rows of the forward returns); ``row_bits``: the row
@@ -59,6 +62,16 @@ def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zco
     exactly 1.0 or NaN), and ``xcorr_stats`` [K][K][3] = (n, mean r, mean \|r\|) of every pair
     over the dates.  On the same preparation and dates as the IC, whatever ``corr_method`` is: the
     factor-to-factor correlation is always Pearson (a Spearman variant is out of scope).
+
+    ``prep`` (an ``afm.xsprep.XsPrep``): every column is first preprocessed across each evaluated
+    date -- winsorised, with ``groups`` (int32 [lda] or [T][lda], labels in [0, ``ngroups``))
+    group-neutralised, standardised (``afm.xsprep.preprocess_grid``) -- over the rows of
+    ``row_bits`` on that date, the cross-section a ``groupby('date').transform`` of the frame sees
+    (not only the rows that also have the three forward returns: then the screen of a frame with
+    ``prep`` is the screen of the preprocessed frame, bit for bit).  The IC, rank IC, layers and
+    correlations then read the preprocessed planes; the result gains ``prep_info`` [nd][K][7] =
+    (n, lo, hi, n_lo, n_hi, mean, std) and ``prep_out`` [K][T][lda].  Without ``prep`` nothing is
+    launched or allocated for it.
 
     Returns device tensors ``ic`` [nd][K][3], ``stats`` [K][3][5] (n, mean, std, IR, t over the
     non-NaN ICs), ``ir_year`` [nyears][K][3], ``nrows``, ``rows_idx``, and the host arrays
@@ -98,6 +111,15 @@ def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zco
     dates_idx = np.ascontiguousarray(dates_idx, dtype=np.int32)
     nd = len(dates_idx)
     d_t = torch.from_numpy(dates_idx).to(dev)
+    prep_res = None
+    if prep is not None:
+        from .xsprep import preprocess_grid, rows_of_mask
+        all_idx, all_n = rows_of_mask(unpack_bits(row_bits, T))
+        prep_res = preprocess_grid(base, cols_t, all_idx, all_n, d_t, T=T, lda=lda, prep=prep,
+                                   zs=zs, zcols=zc_t, col_stride=col_stride, groups=groups,
+                                   ngroups=ngroups, bufs=bufs)
+        base, col_stride, zs, zc_t = prep_res["out"], T * lda, None, None
+        cols_t = torch.arange(K, dtype=i32, device=dev)
     ic = _buffer(bufs, "ic", (nd, K, 3), f64, dev)
     if corr_method == "spearman":
         rank_ic(call, base, col_stride, cols_t, K, zs, zc_t, d_t, nd, rows, rows_idx, nrows, ic,
@@ -118,6 +140,8 @@ def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zco
          ir_year if ny else sscr, sscr)
     out = {"ic": ic, "stats": stats, "ir_year": ir_year, "nrows": nrows, "rows_idx": rows_idx,
            "dates_idx": dates_idx, "years": yr, "year0": y0}
+    if prep_res is not None:
+        out.update(prep_info=prep_res["info"], prep_out=prep_res["out"])
     if layers:
         lm = _buffer(bufs, "layer_mean", (nd, K, 3, 10), f64, dev)
         lc = _buffer(bufs, "layer_cnt", (nd, K, 10), i32, dev)
@@ -230,15 +254,26 @@ class FactorScreen:
     mean and the mean absolute value over the dates of the per-date ``DataFrame.corr()`` of the
     columns, and the number of dates that have it), ``redundant_pairs`` (factor_a, factor_b, mean,
     mean_abs, n: one row per pair a before b with n > 0, by mean_abs descending, ties in column
-    order) and ``select(max_corr, k, return_type)``.  Always Pearson."""
+    order) and ``select(max_corr, k, return_type)``.  Always Pearson.
+
+    ``prep`` (an ``afm.xsprep.XsPrep``) preprocesses every column across each date first --
+    winsorise, neutralise by ``groups`` (the sector of every row: a Series on the frame's index, or
+    the name of a column of the frame, which is then not a factor), standardise -- over the
+    frame's rows of the date: the screen of ``preprocess_factors(factors_df, columns, groups,
+    prep)``, bit for bit, without the trip through the host.  It adds ``prep_info_df`` (date,
+    factor, n, lo, hi, n_lo, n_hi, mean, std: the rows a column has on the date, its clipping
+    bounds and how many rows each clipped, the mean and sd taken out)."""
 
     def __init__(self, factors_df, price_data, columns=None, corr_method="pearson",
-                 layers=False, xcorr=False):
+                 layers=False, xcorr=False, prep=None, groups=None):
+        from .xsprep import _check_prep, frame_columns
+        self.prep = _check_prep(prep) if prep is not None else None
+        self.groups = groups
         self.corr_method = check_corr_method(corr_method)
         self.layers = bool(layers)
         self.xcorr = bool(xcorr)
         self.factors_df = factors_df
-        self.columns = list(columns) if columns is not None else list(factors_df.columns)
+        self.columns = frame_columns(factors_df, columns, groups)
         self.return_type = list(RETURN_TYPES)
         self.price_data = price_data
         self._res = None
@@ -273,8 +308,18 @@ class FactorScreen:
         pm = torch.zeros((T, lda), dtype=torch.bool, device=dev)
         pm[pt, pa] = True
         year = dates.astype("datetime64[Y]").astype(np.int64) + 1970
+        gplane, G = None, 0
+        if self.prep is not None and self.prep.neutralize:
+            from .xsprep import factorize_groups, frame_groups
+            labels = frame_groups(self.factors_df, self.groups)
+            if labels is None:
+                raise ValueError("prep.neutralize needs groups")
+            codes, G = factorize_groups(labels)
+            gplane = torch.full((T, lda), -1, dtype=torch.int32, device=dev)
+            gplane[st, sa] = torch.from_numpy(codes).to(dev)
         r = screen_grid(base, np.arange(K), close, pack_bits(pm), pack_bits(rm), A=A, year=year,
-                        corr_method=self.corr_method, layers=self.layers, xcorr=self.xcorr)
+                        corr_method=self.corr_method, layers=self.layers, xcorr=self.xcorr,
+                        prep=self.prep, groups=gplane, ngroups=max(G, 1))
         r["dates"], r["ids"] = dates, ids
         self._res = r
         ic = r["ic"].cpu().numpy()                                   # [nd][K][3]
@@ -312,6 +357,15 @@ class FactorScreen:
             self._layer_frames(dts, names, types)
         if self.xcorr:
             self._xcorr_frames()
+        if self.prep is not None:
+            from .xsprep import INFO
+            info = r["prep_info"].cpu().numpy().reshape(nd * K, len(INFO))
+            pi = pd.DataFrame(info, columns=INFO)
+            for c in ("n", "n_lo", "n_hi"):
+                pi[c] = pi[c].astype(np.int64)
+            pi.insert(0, "factor", np.tile(names, nd))
+            pi.insert(0, "date", np.repeat(dts.values, K))
+            self.prep_info_df = pi
         return self
 
     def _xcorr_frames(self):
