@@ -14,6 +14,8 @@ Drop-in Python surface (same names, arguments and results as the reference):
 * ``preprocess_factors(df, groups=..., prep=XsPrep(...))`` -- the per-date winsorise / sector-
                                                     neutralise / standardise of every column
                                                     (``groupby('date').transform``)
+* ``combine_factors(df, prices, weights=ICWeights(...))`` -- the rolling IC-weighted composite
+                                                    of the columns (``rolling`` over the ICs)
 * ``PortfolioManager(...)``                       -- KKT:795-970
 * ``split_zscore(all_df)``                       -- KKT:424-458 (z-score + split)
 
@@ -28,6 +30,7 @@ from .regression import (Lasso, LassoCV, LinearRegression, cross_sectional_ols, 
 from .analyzer import AlphaSignalAnalyzer  # noqa: F401
 from .screen import FactorScreen, screen_grid, select_factors  # noqa: F401
 from .xsprep import XsPrep, preprocess_factors, preprocess_grid  # noqa: F401
+from .combine import ICWeights, combine_factors, combine_grid, ic_weights  # noqa: F401
 from .portfolio import PortfolioManager, mean_variance_weights  # noqa: F401
 from .zscore import split_zscore, zscore_grid  # noqa: F401
 
@@ -35,4 +38,5 @@ __all__ = ["compute_factors", "factor_panel", "FACTOR_NAMES", "PanelGrid", "pack
            "unpack_bits", "LinearRegression", "Lasso", "LassoCV", "lasso_path",
            "cross_sectional_ols", "AlphaSignalAnalyzer", "FactorScreen", "screen_grid",
            "select_factors", "PortfolioManager", "split_zscore", "zscore_grid", "XsPrep",
-           "preprocess_factors", "preprocess_grid"]
+           "preprocess_factors", "preprocess_grid", "ICWeights", "ic_weights", "combine_grid",
+           "combine_factors"]

@@ -48,10 +48,12 @@ def _buffer(bufs, name, shape, dtype, dev):
 
 
 def rank_ic(call, base, col_stride, cols_t, K, zs, zc_t, d_t, nd, rows, rows_idx, nrows, ic,
-            bufs=None):
+            bufs=None, ranked=False):
     """The Spearman IC of K columns on prepared rows into ``ic`` [nd][K][3]: the return ranks of
     the evaluated dates once (afm_rank_returns_f64), then every (date, column)
-    (afm_screen_rank_ic_f64).  Arguments as afm_screen_ic_f64's; work buffers in ``bufs``."""
+    (afm_screen_rank_ic_f64).  Arguments as afm_screen_ic_f64's; work buffers in ``bufs``.
+    ``ranked``: ``bufs`` still holds the return ranks of a call with the same ``d_t``, ``rows``
+    and ``nrows``, and they are not taken again."""
     import torch
     if nd == 0:
         return ic
@@ -61,7 +63,8 @@ def rank_ic(call, base, col_stride, cols_t, K, zs, zc_t, d_t, nd, rows, rows_idx
     scr = _buffer(bufs, "rank_scratch", (max(words, 1),), torch.int64, dev)
     rrank = _buffer(bufs, "rrank", (3, T, lda), torch.int32, dev)
     rsum = _buffer(bufs, "rsum", (T, 3), torch.int64, dev)
-    call("afm_rank_returns_f64", T, lda, d_t, nd, rows, nrows, rrank, rsum, scr)
+    if not (ranked and bufs is not None):
+        call("afm_rank_returns_f64", T, lda, d_t, nd, rows, nrows, rrank, rsum, scr)
     call("afm_screen_rank_ic_f64", base, col_stride, T, lda, cols_t, K, zs, zc_t, d_t, nd, rows,
          rows_idx, nrows, rrank, rsum, scr, ic)
     return ic

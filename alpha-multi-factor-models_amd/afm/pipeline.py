@@ -1040,7 +1040,7 @@ class Pipeline:
 
     def factor_screen(self, split: str = "train", z: bool = True, columns=None,
                       corr_method: str = "pearson", layers: bool = False,
-                      xcorr: bool = False, prep=None, groups=None) -> dict:
+                      xcorr: bool = False, prep=None, groups=None, combine=None) -> dict:
         """Factor screening on the last ``step()``'s resident panel (one GPU): the per-date IC
         (``corr_method``: 'pearson', or 'spearman' for the rank IC) of every column against
         return_1 / 2 / 5, its per-year IR and whole-sample
@@ -1080,6 +1080,13 @@ class Pipeline:
         (``screen_grid(..., prep=...)``).  ``groups``: a host array [A] of group (sector) labels of
         any dtype, one per security (default: the grid's ``group``; NaN: in no group).  The result
         gains ``prep_info`` [nd][K][7] = (n, lo, hi, n_lo, n_hi, mean, std).
+
+        ``combine`` (an ``afm.combine.ICWeights``): the columns are combined into one signal, on
+        every evaluated date weighted by their rolling ICs of the dates before it
+        (``screen_grid(..., combine=...)``).  Host arrays ``weights`` [nd][K], ``weights_info``
+        [nd][3], ``composite_ic`` [nd][3] and ``composite_stats`` [3][5]; the plane stays on the
+        device as ``composite_dev`` [dates of the split's sub-grid][lda], whose row 0 is calendar
+        date ``composite_t0`` (the buffer is reused by the next call).
 
         Not the multi-GPU pipeline."""
         import torch
@@ -1130,16 +1137,20 @@ class Pipeline:
                             zs=self.zs if z else None, zcols=zcols, col_stride=T * lda,
                             year=years[a0:t1], bufs=b, corr_method=corr_method,
                             layers=layers, xcorr=xcorr, prep=prep, groups=gdev,
-                            ngroups=max(G, 1))
+                            ngroups=max(G, 1), combine=combine)
             keys = ("ic", "stats", "ir_year") + (("layer_mean", "layer_cnt", "port", "cum_layer",
                                                   "ls", "cum_port") if layers else ())
             if xcorr:
                 keys += ("xcorr_stats",)
             if prep is not None:
                 keys += ("prep_info",)
+            if combine is not None:
+                keys += ("weights", "weights_info", "composite_ic", "composite_stats")
             out = {k: r[k].cpu().numpy() for k in keys}
             if xcorr:
                 out["xcorr_dev"] = r["xcorr"]
+            if combine is not None:
+                out["composite_dev"], out["composite_t0"] = r["composite"], a0
             nrows = np.zeros(T, dtype=np.int32)
             nrows[a0:t1] = r["nrows"].cpu().numpy()
         out.update(nrows=nrows, dates_idx=r["dates_idx"] + np.int32(a0), years=r["years"],

@@ -16,6 +16,9 @@ over the dates, and ``select_factors``, a greedy "best IR first, drop what is to
 what is kept" choice of columns (csrc/xcorr.hip, include/afm_xcorr.h).  With ``prep=XsPrep(...)``
 every column is first winsorised, group-neutralised and standardised across each date
 (afm/xsprep.py, csrc/xsprep.hip, include/afm_xsprep.h) and all of the above rate the result.
+With ``combine=ICWeights(...)`` the columns are combined into one signal -- on every date weighted
+by their rolling ICs of the past -- and the composite is rated next to its ingredients
+(afm/combine.py, csrc/combine.hip, include/afm_combine.h).
 ``FactorScreen`` is the frame interface beside ``AlphaSignalAnalyzer``.
 
 Out of scope: the multi-GPU pipeline.
@@ -34,7 +37,7 @@ STATS = ["n", "mean", "std", "IR", "t"]
 def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zcols=None,
                 col_stride=None, dates_idx=None, year=None, bufs=None,
                 corr_method="pearson", layers=False, xcorr=False, prep=None, groups=None,
-                ngroups=0) -> dict:
+                ngroups=0, combine=None) -> dict:
     """Device-level screen on grids.  ``base``: the panel, plane k of the screen at ``base +
     cols[k] * col_stride`` ([T][lda] each; ``col_stride`` defaults to T * lda); ``close`` [T][lda]
     with ``price_bits`` presence (the price rows of the forward returns); ``row_bits``: the row
@@ -73,6 +76,16 @@ def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zco
     (n, lo, hi, n_lo, n_hi, mean, std) and ``prep_out`` [K][T][lda].  Without ``prep`` nothing is
     launched or allocated for it.
 
+    ``combine`` (an ``afm.combine.ICWeights``): after the IC, ``weights`` [nd][K] and
+    ``weights_info`` [nd][3] = (n_active, n_dates, sum \|raw\|) -- the rolling weights of every
+    evaluated date from the ICs (those of ``corr_method``) of the dates before it
+    (``afm.combine.ic_weights``); ``composite`` [T][lda] and ``composite_cnt`` -- sum w x / sum
+    \|w\| over the screen's shared rows (``rows_idx`` / ``nrows``) of what the IC read, ``prep_out``
+    when ``prep`` is given, else the raw / z values (``afm.combine.combine_grid``); and
+    ``composite_ic`` [nd][3], ``composite_stats`` [3][5]: the IC (or rank IC) and summary kernels
+    on the composite as a one-column panel.  ``dates_idx`` must be ascending (the window of a date
+    is the positions before it).  Without ``combine`` nothing is launched or allocated for it.
+
     Returns device tensors ``ic`` [nd][K][3], ``stats`` [K][3][5] (n, mean, std, IR, t over the
     non-NaN ICs), ``ir_year`` [nyears][K][3], ``nrows``, ``rows_idx``, and the host arrays
     ``dates_idx``, ``years``, ``year0``.  ``bufs``: a dict that keeps the work buffers between
@@ -110,6 +123,12 @@ def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zco
         dates_idx = np.flatnonzero(nrows.cpu().numpy() > 0)
     dates_idx = np.ascontiguousarray(dates_idx, dtype=np.int32)
     nd = len(dates_idx)
+    if combine is not None:
+        from .combine import _check_spec, screen_composite
+        _check_spec(combine)
+        if nd > 1 and not (np.diff(dates_idx) > 0).all():
+            raise ValueError("combine: dates_idx must be ascending (the rolling window of a date "
+                             "is the evaluated dates before it)")
     d_t = torch.from_numpy(dates_idx).to(dev)
     prep_res = None
     if prep is not None:
@@ -122,8 +141,10 @@ def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zco
         cols_t = torch.arange(K, dtype=i32, device=dev)
     ic = _buffer(bufs, "ic", (nd, K, 3), f64, dev)
     if corr_method == "spearman":
+        # (without a caller's dict the return ranks still live until the composite has used them)
+        rank_bufs = bufs if bufs is not None or combine is None else {}
         rank_ic(call, base, col_stride, cols_t, K, zs, zc_t, d_t, nd, rows, rows_idx, nrows, ic,
-                bufs)
+                rank_bufs)
     else:
         call("afm_screen_ic_f64", base, col_stride, T, lda, cols_t, K, zs, zc_t, d_t, nd, rows,
              rows_idx, nrows, ic)
@@ -142,6 +163,10 @@ def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zco
            "dates_idx": dates_idx, "years": yr, "year0": y0}
     if prep_res is not None:
         out.update(prep_info=prep_res["info"], prep_out=prep_res["out"])
+    if combine is not None:
+        out.update(screen_composite(call, combine, ic, base, col_stride, cols_t, zs, zc_t, d_t,
+                                    rows, rows_idx, nrows, corr_method, bufs,
+                                    rank_bufs if corr_method == "spearman" else None))
     if layers:
         lm = _buffer(bufs, "layer_mean", (nd, K, 3, 10), f64, dev)
         lc = _buffer(bufs, "layer_cnt", (nd, K, 10), i32, dev)
@@ -262,11 +287,22 @@ class FactorScreen:
     frame's rows of the date: the screen of ``preprocess_factors(factors_df, columns, groups,
     prep)``, bit for bit, without the trip through the host.  It adds ``prep_info_df`` (date,
     factor, n, lo, hi, n_lo, n_hi, mean, std: the rows a column has on the date, its clipping
-    bounds and how many rows each clipped, the mean and sd taken out)."""
+    bounds and how many rows each clipped, the mean and sd taken out).
+
+    ``combine`` (an ``afm.combine.ICWeights``) combines the columns into one signal, on every date
+    weighted by their rolling ICs of the dates before it, and adds ``weights_df`` (date, factor,
+    weight; the dates without weights dropped), ``composite`` (a Series named ``"composite"`` on
+    (date, id) over the frame's rows that have the three forward returns, NaN dropped) and
+    ``composite_summary`` (Type, n, mean, std, IR, t of the composite's own IC: does the
+    combination beat its best column?)."""
 
     def __init__(self, factors_df, price_data, columns=None, corr_method="pearson",
-                 layers=False, xcorr=False, prep=None, groups=None):
+                 layers=False, xcorr=False, prep=None, groups=None, combine=None):
         from .xsprep import _check_prep, frame_columns
+        if combine is not None:
+            from .combine import _check_spec
+            _check_spec(combine)
+        self.combine = combine
         self.prep = _check_prep(prep) if prep is not None else None
         self.groups = groups
         self.corr_method = check_corr_method(corr_method)
@@ -319,7 +355,7 @@ class FactorScreen:
             gplane[st, sa] = torch.from_numpy(codes).to(dev)
         r = screen_grid(base, np.arange(K), close, pack_bits(pm), pack_bits(rm), A=A, year=year,
                         corr_method=self.corr_method, layers=self.layers, xcorr=self.xcorr,
-                        prep=self.prep, groups=gplane, ngroups=max(G, 1))
+                        prep=self.prep, groups=gplane, ngroups=max(G, 1), combine=self.combine)
         r["dates"], r["ids"] = dates, ids
         self._res = r
         ic = r["ic"].cpu().numpy()                                   # [nd][K][3]
@@ -366,6 +402,20 @@ class FactorScreen:
             pi.insert(0, "factor", np.tile(names, nd))
             pi.insert(0, "date", np.repeat(dts.values, K))
             self.prep_info_df = pi
+        if self.combine is not None:
+            w = r["weights"].cpu().numpy()                           # [nd][K]
+            keep = np.repeat(~np.isnan(w).all(axis=1), K)
+            self.weights_df = pd.DataFrame({
+                "date": np.repeat(dts.values, K)[keep],
+                "factor": np.tile(names, nd)[keep],
+                "weight": w.reshape(-1)[keep]})
+            comp = pd.Series(r["composite"][st, sa].cpu().numpy(), index=self.factors_df.index,
+                             name="composite")
+            self.composite = comp.dropna()
+            cs = pd.DataFrame(r["composite_stats"].cpu().numpy(), columns=STATS)
+            cs["n"] = cs["n"].astype(np.int64)
+            cs.insert(0, "Type", types)
+            self.composite_summary = cs
         return self
 
     def _xcorr_frames(self):
