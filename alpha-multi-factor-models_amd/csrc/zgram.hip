@@ -903,6 +903,15 @@ extern "C" int afm_zpool_f64(afm_ctx* ctx, const double* base, int64_t col_strid
     ZGramArgs g{base, col_stride, lda, cols, zcols, p, ycol, zid, zs, bits, t0, nt, 1, 1, blk0,
                 64, a_end, nrb, nchunk, part, zgram_nt(p) == 2 ? 1 : 0};
     AFM_CHECK_ARG(zs != nullptr, "afm_zpool_f64 needs zs");
+    if (nt == 0) {
+        // No dates: every leaf is the empty sum.  Written here, without a launch: the kernel
+        // would stage one all-masked slot per leaf at date t0, and the NT = 7 producer loads a
+        // masked slot's cell [t0][0] and presence word [t0 >> 6][0] -- past the planes when
+        // t0 = T (and past `bits` when T is a multiple of 64).
+        AFM_HIP(hipMemsetAsync(part, 0, (size_t)nrb * nchunk * afm_zgram_part_bytes(p),
+                               ctx->stream));
+        return AFM_OK;
+    }
     return zgram_nt(p) == 2 ? launch_zgram<2, 1, true>(ctx, g, (int64_t)nrb * nchunk, grid)
                             : launch_zgram<7, 1, true>(ctx, g, (int64_t)nrb * nchunk, grid);
 }

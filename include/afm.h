@@ -364,7 +364,17 @@ int afm_zgram_part_bytes(int p);
  * afm_zpool_f64 -- one partial per (row-block r, date chunk c): the 64 assets [blk0 + 64r, +64)
  *   at every date of chunk c of [t0, t0+nt) (nchunk equal chunks); part [nrb][nchunk][part].
  *   The pooled Gram of every (date, asset) row (the design matrix of KKT:583 / 606): a
- *   workgroup keeps one row-block's {mu, 1/sd} in registers across its dates. */
+ *   workgroup keeps one row-block's {mu, 1/sd} in registers across its dates.
+ * An item without rows (an empty date or chunk, a block past a_end) gets an all-zero Gram.
+ * nt = 0: afm_zgram_f64 owns no partial and writes nothing; afm_zpool_f64 writes its nrb * nchunk
+ * partials as zeros.  Cells without a row are never used, whatever they hold (NaN, inf).
+ * Limits the caller must keep (cols and zcols are DEVICE arrays, so they are NOT validated): the
+ * kernels pack (plane, zs row) of a column into one 32-bit word and address both through 32-bit
+ * byte offsets, so every plane index (cols[j], ycol) must be below 65536, every zs row (zcols[j],
+ * zid) below 32768, and zs_rows * lda * 16 < 2^32 for the largest zs row + 1 = zs_rows.  The
+ * host check assumes at most 112 zs rows (lda * 16 * 112 < 2^32), which holds for zcols = NULL
+ * (rows 0 .. p <= 106) but not for a zcols that points further: then the bound is the caller's.
+ * Likewise (t0 + nt) * lda * 8 < 2^32 (checked). */
 int afm_zgram_f64(afm_ctx* ctx, const double* base, int64_t col_stride, int64_t lda,
                   const int32_t* cols, const int32_t* zcols, int p, int ycol, const double* zs,
                   int zid, const uint64_t* bits, int64_t t0, int64_t nt, int nblk, int64_t blk0,
