@@ -1,6 +1,6 @@
 """ctypes binding of libafm.so (the C-ABI declared in include/afm.h, include/afm_mv.h,
 include/afm_screen.h, include/afm_rankic.h, include/afm_seams.h, include/afm_screen_layers.h,
-include/afm_xcorr.h, include/afm_xsprep.h and include/afm_combine.h).
+include/afm_xcorr.h, include/afm_xsprep.h, include/afm_combine.h and include/afm_turnover.h).
 
 The product path has no CPU fallback: if the library is missing or no GPU is visible, every
 call raises.  ``make -C alpha-multi-factor-models_amd`` (or ``__graft_entry__.build()``) builds
@@ -162,7 +162,16 @@ SIGNATURES_COMBINE = {
     "afm_combine_f64": ("status", "ctx f64* i64 i64 i64 i32* int f64* i32* i32* i64 i32* i32* f64* "
                                   "i64 f64* i32*"),
 }
-COMBINE_TABLES = PREP_TABLES + (SIGNATURES_COMBINE,)   # what lib() declares and Context.call resolves
+COMBINE_TABLES = PREP_TABLES + (SIGNATURES_COMBINE,)
+# ... and for include/afm_turnover.h, the rank autocorrelation and turnover of the screened columns
+# (tests/test_abi_turnover.py); host:i32*: a host int32_t array
+SIGNATURES_TURNOVER = {
+    "afm_screen_turnover_scratch_bytes": ("i64", "i64 int i64"),
+    "afm_screen_turnover_f64": ("status", "ctx f64* i64 i64 i64 i32* int f64* i32* i32* i64 i32* "
+                                          "i32* host:i32* int f64* i32* f64* i64*"),
+    "afm_screen_turnover_summary_f64": ("status", "ctx f64* i32* f64* i64 int int f64*"),
+}
+TURNOVER_TABLES = COMBINE_TABLES + (SIGNATURES_TURNOVER,)   # what lib() declares and Context.call resolves
 _RESTYPE = {"status": I32, "int": I32, "i64": I64, "str": ctypes.c_char_p}
 _ARGTYPE = {"int": I32, "i64": I64, "f64": DBL, "str": ctypes.c_char_p}    # every pointer: void*
 
@@ -184,7 +193,7 @@ def lib():
                     raise ImportError(f"{LIB_PATH} is not built: run `make -C "
                                       f"{os.path.dirname(HERE)}` (hipcc, gfx950)")
                 L = ctypes.CDLL(LIB_PATH)
-                for table in COMBINE_TABLES:
+                for table in TURNOVER_TABLES:
                     for name, (res, params) in table.items():
                         f = getattr(L, name)
                         f.restype = _RESTYPE[res]
@@ -230,7 +239,7 @@ def _plans(device: int) -> dict:
     negative = (0).__gt__
     failed = {"status": bool, "int": negative, "i64": negative, "str": lambda s: s is None}
     plans = {}
-    for name, (res, params) in (item for table in COMBINE_TABLES for item in table.items()):
+    for name, (res, params) in (item for table in TURNOVER_TABLES for item in table.items()):
         toks = params.split()
         takes_ctx = toks[:1] == ["ctx"]
         convs = tuple(_device_buffer(buffer[t], device, f"{name} argument {i}") if t in buffer

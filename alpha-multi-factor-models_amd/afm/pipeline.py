@@ -1040,7 +1040,8 @@ class Pipeline:
 
     def factor_screen(self, split: str = "train", z: bool = True, columns=None,
                       corr_method: str = "pearson", layers: bool = False,
-                      xcorr: bool = False, prep=None, groups=None, combine=None) -> dict:
+                      xcorr: bool = False, prep=None, groups=None, combine=None,
+                      turnover=None) -> dict:
         """Factor screening on the last ``step()``'s resident panel (one GPU): the per-date IC
         (``corr_method``: 'pearson', or 'spearman' for the rank IC) of every column against
         return_1 / 2 / 5, its per-year IR and whole-sample
@@ -1087,6 +1088,12 @@ class Pipeline:
         [nd][3], ``composite_ic`` [nd][3] and ``composite_stats`` [3][5]; the plane stays on the
         device as ``composite_dev`` [dates of the split's sub-grid][lda], whose row 0 is calendar
         date ``composite_t0`` (the buffer is reused by the next call).
+
+        ``turnover`` (an ``afm.turnover.Turnover``): how much every column changes against the
+        evaluated date ``lag`` positions earlier (``screen_grid(..., turnover=...)``).  Host arrays
+        ``rank_ac`` [nd][K][L], ``turnover_counts`` [nd][K][L][5], ``port_turnover`` [nd][K][L] and
+        ``turnover_stats`` [K][L][4][2]; with ``combine`` also the composite's, the names with
+        ``composite_`` in front.
 
         Not the multi-GPU pipeline."""
         import torch
@@ -1137,7 +1144,7 @@ class Pipeline:
                             zs=self.zs if z else None, zcols=zcols, col_stride=T * lda,
                             year=years[a0:t1], bufs=b, corr_method=corr_method,
                             layers=layers, xcorr=xcorr, prep=prep, groups=gdev,
-                            ngroups=max(G, 1), combine=combine)
+                            ngroups=max(G, 1), combine=combine, turnover=turnover)
             keys = ("ic", "stats", "ir_year") + (("layer_mean", "layer_cnt", "port", "cum_layer",
                                                   "ls", "cum_port") if layers else ())
             if xcorr:
@@ -1146,6 +1153,9 @@ class Pipeline:
                 keys += ("prep_info",)
             if combine is not None:
                 keys += ("weights", "weights_info", "composite_ic", "composite_stats")
+            if turnover is not None:
+                tk = ("rank_ac", "turnover_counts", "port_turnover", "turnover_stats")
+                keys += tk + (tuple("composite_" + k for k in tk) if combine is not None else ())
             out = {k: r[k].cpu().numpy() for k in keys}
             if xcorr:
                 out["xcorr_dev"] = r["xcorr"]

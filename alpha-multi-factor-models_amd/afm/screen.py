@@ -18,7 +18,10 @@ every column is first winsorised, group-neutralised and standardised across each
 (afm/xsprep.py, csrc/xsprep.hip, include/afm_xsprep.h) and all of the above rate the result.
 With ``combine=ICWeights(...)`` the columns are combined into one signal -- on every date weighted
 by their rolling ICs of the past -- and the composite is rated next to its ingredients
-(afm/combine.py, csrc/combine.hip, include/afm_combine.h).
+(afm/combine.py, csrc/combine.hip, include/afm_combine.h).  With ``turnover=Turnover(...)`` it
+also says how much every column changes from one date to an earlier one -- the rank
+autocorrelation, the turnover of the extreme layers and of the top-10 book -- which is what the
+gross returns above have to pay for (afm/turnover.py, csrc/turnover.hip, include/afm_turnover.h).
 ``FactorScreen`` is the frame interface beside ``AlphaSignalAnalyzer``.
 
 Out of scope: the multi-GPU pipeline.
@@ -37,7 +40,7 @@ STATS = ["n", "mean", "std", "IR", "t"]
 def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zcols=None,
                 col_stride=None, dates_idx=None, year=None, bufs=None,
                 corr_method="pearson", layers=False, xcorr=False, prep=None, groups=None,
-                ngroups=0, combine=None) -> dict:
+                ngroups=0, combine=None, turnover=None) -> dict:
     """Device-level screen on grids.  ``base``: the panel, plane k of the screen at ``base +
     cols[k] * col_stride`` ([T][lda] each; ``col_stride`` defaults to T * lda); ``close`` [T][lda]
     with ``price_bits`` presence (the price rows of the forward returns); ``row_bits``: the row
@@ -86,6 +89,14 @@ def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zco
     on the composite as a one-column panel.  ``dates_idx`` must be ascending (the window of a date
     is the positions before it).  Without ``combine`` nothing is launched or allocated for it.
 
+    ``turnover`` (an ``afm.turnover.Turnover``): after the IC, on what the IC read (``prep_out``
+    when ``prep`` is given, else the raw / z values) over the screen's shared rows, ``rank_ac``
+    [nd][K][L], ``turnover_counts`` [nd][K][L][5] (int32), ``port_turnover`` [nd][K][L] and
+    ``turnover_stats`` [K][L][4][2] of every (date, column, lag) against the evaluated date ``lag``
+    positions earlier (``afm.turnover.turnover_grid``); with ``combine`` the same of the composite
+    as a one-column panel, the names with ``composite_`` in front.  ``dates_idx`` must be
+    ascending.  Without ``turnover`` nothing is launched or allocated for it.
+
     Returns device tensors ``ic`` [nd][K][3], ``stats`` [K][3][5] (n, mean, std, IR, t over the
     non-NaN ICs), ``ir_year`` [nyears][K][3], ``nrows``, ``rows_idx``, and the host arrays
     ``dates_idx``, ``years``, ``year0``.  ``bufs``: a dict that keeps the work buffers between
@@ -129,6 +140,12 @@ def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zco
         if nd > 1 and not (np.diff(dates_idx) > 0).all():
             raise ValueError("combine: dates_idx must be ascending (the rolling window of a date "
                              "is the evaluated dates before it)")
+    if turnover is not None:
+        from .turnover import _check_spec as _check_turnover, turnover_grid
+        _check_turnover(turnover)
+        if nd > 1 and not (np.diff(dates_idx) > 0).all():
+            raise ValueError("turnover: dates_idx must be ascending (a lag counts evaluated dates "
+                             "back)")
     d_t = torch.from_numpy(dates_idx).to(dev)
     prep_res = None
     if prep is not None:
@@ -167,6 +184,14 @@ def screen_grid(base, cols, close, price_bits, row_bits, *, A: int, zs=None, zco
         out.update(screen_composite(call, combine, ic, base, col_stride, cols_t, zs, zc_t, d_t,
                                     rows, rows_idx, nrows, corr_method, bufs,
                                     rank_bufs if corr_method == "spearman" else None))
+    if turnover is not None:
+        out.update(turnover_grid(base, cols_t, rows_idx, nrows, dates_idx, T=T, lda=lda,
+                                 spec=turnover, zs=zs, zcols=zc_t, col_stride=col_stride,
+                                 bufs=bufs))
+        if combine is not None:
+            out.update(turnover_grid(out["composite"], np.zeros(1, dtype=np.int32), rows_idx,
+                                     nrows, dates_idx, T=T, lda=lda, spec=turnover, bufs=bufs,
+                                     prefix="composite_"))
     if layers:
         lm = _buffer(bufs, "layer_mean", (nd, K, 3, 10), f64, dev)
         lc = _buffer(bufs, "layer_cnt", (nd, K, 10), i32, dev)
@@ -294,14 +319,33 @@ class FactorScreen:
     weight; the dates without weights dropped), ``composite`` (a Series named ``"composite"`` on
     (date, id) over the frame's rows that have the three forward returns, NaN dropped) and
     ``composite_summary`` (Type, n, mean, std, IR, t of the composite's own IC: does the
-    combination beat its best column?)."""
+    combination beat its best column?).
+
+    ``turnover`` (an ``afm.turnover.Turnover``) adds how stable every column is against the date
+    ``lag`` evaluated dates earlier: ``turnover_df`` (date, factor, lag, rank_autocorr -- the
+    correlation of the two dates' ranks over the securities ranked on both --, top_turnover and
+    bottom_turnover -- the share of layer 10 / layer 1 that was not in it on the earlier date --,
+    port_turnover -- 0.5 sum \\|w1 - w0\\| of the factor-weighted top-10 book --, n_joint; the rows
+    with a date ``lag`` positions back; by date, factor in column order, lag) and
+    ``turnover_summary`` (factor, lag, n, and the means of the four over their non-NaN dates; ``n``
+    counts the dates with a rank autocorrelation; by the mean port_turnover of the smallest lag
+    ascending, ties in column order, NaN last, the lags of a factor together).  With
+    ``layers=True`` and lag 1 among the lags, ``turnover_summary`` gains ``breakeven_cost`` on the
+    lag-1 rows (NaN on the others): the mean of the column's non-NaN top-10 ``return_1`` divided
+    by its mean lag-1 port_turnover, the ``trading_cost_rate`` at which the daily rebalanced
+    top-10 book nets zero (KKT:887-889).  With ``combine``, ``composite_turnover_summary`` (lag, n
+    and the four means of the composite)."""
 
     def __init__(self, factors_df, price_data, columns=None, corr_method="pearson",
-                 layers=False, xcorr=False, prep=None, groups=None, combine=None):
+                 layers=False, xcorr=False, prep=None, groups=None, combine=None, turnover=None):
         from .xsprep import _check_prep, frame_columns
         if combine is not None:
             from .combine import _check_spec
             _check_spec(combine)
+        if turnover is not None:
+            from .turnover import _check_spec as _check_turnover
+            _check_turnover(turnover)
+        self.turnover = turnover
         self.combine = combine
         self.prep = _check_prep(prep) if prep is not None else None
         self.groups = groups
@@ -355,7 +399,8 @@ class FactorScreen:
             gplane[st, sa] = torch.from_numpy(codes).to(dev)
         r = screen_grid(base, np.arange(K), close, pack_bits(pm), pack_bits(rm), A=A, year=year,
                         corr_method=self.corr_method, layers=self.layers, xcorr=self.xcorr,
-                        prep=self.prep, groups=gplane, ngroups=max(G, 1), combine=self.combine)
+                        prep=self.prep, groups=gplane, ngroups=max(G, 1), combine=self.combine,
+                        turnover=self.turnover)
         r["dates"], r["ids"] = dates, ids
         self._res = r
         ic = r["ic"].cpu().numpy()                                   # [nd][K][3]
@@ -416,7 +461,30 @@ class FactorScreen:
             cs["n"] = cs["n"].astype(np.int64)
             cs.insert(0, "Type", types)
             self.composite_summary = cs
+        if self.turnover is not None:
+            self._turnover_frames(dts, names)
         return self
+
+    def _turnover_frames(self, dts, names):
+        from .turnover import sort_summary, turnover_frames
+        r, spec = self._res, self.turnover
+        K, L = len(names), len(spec.lags)
+        self.turnover_df, summary = turnover_frames(r, dts.values, names, spec)
+        if self.layers and spec.lags[0] == 1:
+            # the mean gross top-10 return_1 over the mean lag-1 turnover of the same book
+            port = r["port"].cpu().numpy()[:, :, 0]                  # [nd][K]
+            turn = r["turnover_stats"].cpu().numpy()[:, 0, 3, 1]     # [K]
+            be = np.full((K, L), np.nan)
+            for k in range(K):
+                v = port[:, k][~np.isnan(port[:, k])]
+                if len(v):
+                    with np.errstate(all="ignore"):
+                        be[k, 0] = np.float64(v.mean()) / turn[k]
+            summary["breakeven_cost"] = be.reshape(-1)
+        self.turnover_summary = sort_summary(summary, K, L)
+        if self.combine is not None:
+            _, cs = turnover_frames(r, dts.values, ["composite"], spec, prefix="composite_")
+            self.composite_turnover_summary = cs.drop(columns="factor")
 
     def _xcorr_frames(self):
         import pandas as pd
