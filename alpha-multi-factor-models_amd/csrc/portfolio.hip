@@ -39,6 +39,7 @@ typedef unsigned long long u64;
 constexpr int kT = 256;        // threads per workgroup
 constexpr int kMaxK = 128;     // book-size cap; the global book arrays are [nd][2][kMaxK]
 constexpr int kMaxWords = 512; // lda <= 32768 assets
+static_assert(kMaxK == AFM_MAX_BOOK, "include/afm.h sizes the callers' book arrays: AFM_MAX_BOOK");
 
 struct RebArgs {
     int64_t T, lda, A;
@@ -67,7 +68,8 @@ struct RebArgs {
     double* sums;             // [nd][4]: long_ret, short_ret, den_long, den_short
     int32_t* upos;            // [nd][2][2][kMaxK]: union position vs prev / vs next (-1 absent)
     int64_t* usize;           // [nd][2]: |P_prev U P_i|, |P_i U P_next|
-    int32_t* status;          // [nd] (zeroed by the launcher): |1 QP iteration cap, 2 k > cap
+    int32_t* status;          // [nd] (zeroed by the launcher): |1 QP iteration cap or a non-finite
+                              // covariance (weights NaN), 2 k > cap
     // the return term of the mean-variance instantiations (afm_rebalance_mv_f64; unread otherwise)
     const double* mu;         // [T][lda] expected returns, or null: the history window's mean
     double gamma;             // risk tolerance
@@ -1818,11 +1820,18 @@ __global__ __launch_bounds__(64) void turnover_terms_kernel(int64_t nd, const in
     }
     __syncthreads();
     if (active) {
+        // a name in both books of one date holds the short position (the reference assigns the
+        // short book last, KKT:881-882) and is one slot of the union: its long-book copy is
+        // skipped, and ns below ends on the short side (the last match)
         for (int e = tid; e < 2 * kp; e += 64) {     // previous members predicted today
             const int side = e / kp, q = e % kp;
             const int a = bk_prev[e];
             const int pz = upos[(((i - 1) * 2 + side) * 2 + 1) * kMaxK + q];
             if (pz < 0) continue;
+            bool dup = false;
+            if (side == 0)
+                for (int q2 = kp; q2 < 2 * kp; ++q2) dup |= bk_prev[q2] == a;
+            if (dup) continue;
             int ns = 2;
             for (int q2 = 0; q2 < 2 * k; ++q2)
                 if (bk_cur[q2] == a) ns = q2 / k;
@@ -1836,6 +1845,8 @@ __global__ __launch_bounds__(64) void turnover_terms_kernel(int64_t nd, const in
             const int pz = upos[((i * 2 + side) * 2 + 0) * kMaxK + q];
             if (pz < 0) continue;
             bool inprev = false;
+            if (side == 0)                           // (its short-book copy carries the term)
+                for (int q2 = k; q2 < 2 * k; ++q2) inprev |= bk_cur[q2] == a;
             for (int q2 = 0; q2 < 2 * kp; ++q2)
                 if (bk_prev[q2] == a) inprev = true;
             if (inprev) continue;
@@ -2012,18 +2023,23 @@ __global__ __launch_bounds__(256) void turnover_terms_wave_kernel(int64_t nd, co
             a = books[((int64_t)si * 2 + side) * kMaxK + q];
             pz = upos[(((int64_t)i * 2 + side) * 2 + 0) * kMaxK + q];
         }
+        // A name in BOTH books of one date (the long and the short threshold inside one tie: a
+        // constant or coarsely quantised predictor) holds the short position -- the reference
+        // assigns the short book last (KKT:881-882) -- and is one slot of the union, so one term:
+        // its long-book copy drops out (dup), and ns below ends on the short side (the last match).
         int ns = 2;
-        bool inprev = false;
+        bool inprev = false, dup = false;
         for (uint64_t b = __ballot(isp || isc); b; b &= b - 1) {   // (uniform loop)
             const int j = __builtin_ctzll(b);
             const int aj = wv_read(a, j), sj = wv_read(side, j);
             if (aj == a) {
                 if (j >= 32) ns = sj;
                 else inprev = true;
+                if ((j >= 32) == (lane >= 32) && sj > side) dup = true;
             }
         }
         const int code = isp ? side * 3 + ns : 2 * 3 + side;
-        const bool valid = (isp || (isc && !inprev)) && pz >= 0;
+        const bool valid = (isp || (isc && !inprev)) && pz >= 0 && !dup;
         const uint64_t vm = __ballot(valid);
         const int m = __popcll(vm);
         const int key = valid ? np_key(n, pz) : 0x7fffffff;

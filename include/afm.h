@@ -199,8 +199,10 @@ int afm_lasso_cd_f64(afm_ctx* ctx, const double* gram, int p, double alpha_n, do
                      int max_iter, double tol, int positive, double* w, double* info);
 
 /* ---- K1-K3: rebalance, weights, PnL -- replaces PortfolioManager (KKT:795-892) ---------------
- * Book arrays are [nd][2][AFM_MAX_BOOK] (long book, short book). */
-#define AFM_MAX_BOOK 64
+ * Book arrays are [nd][2][AFM_MAX_BOOK] (long book, short book): AFM_MAX_BOOK is the row stride
+ * of books, weights and upos whatever top_n is, and the library's book-size cap (kMaxK of
+ * csrc/portfolio.hip, which asserts the two equal; afm.portfolio.MAX_BOOK in Python). */
+#define AFM_MAX_BOOK 128
 /* One call per set of rebalance dates (grid date indices `dates`, ascending, DEVICE int32[nd]).
  * pred [T][lda] (NaN = no prediction); trad_bits: present in all_df AND in_trading_universe=='Y';
  * hist/hist_bits: the history returns (df_train_y) and their presence; history rows are
@@ -210,8 +212,10 @@ int afm_lasso_cd_f64(afm_ctx* ctx, const double* gram, int p, double alpha_n, do
  * prediction, ties by ascending index), weights (exact min-variance, sum 1, lo <= w <= hi),
  * sums[nd][4] = {sum(tmr*w) long, short (numpy pairwise), sum(w*close) long, short (sequential)},
  * upos[nd][2][2][AFM_MAX_BOOK] / usize[nd][2]: members' positions in the id-union with the
- * previous / next date's prediction set (turnover alignment), status[nd] (0 ok, 1 QP cap,
- * 2 book larger than AFM_MAX_BOOK).  top_n <= AFM_MAX_BOOK. */
+ * previous / next date's prediction set (turnover alignment; -1: the member is not in that
+ * set), status[nd] (0 ok, |1 QP iteration cap or a non-finite covariance: weights NaN,
+ * 2 book larger than AFM_MAX_BOOK).  top_n <= AFM_MAX_BOOK.  Entries past a date's k_out are
+ * not written, and a date with k_out = 0 writes only k_out, sums {0, 0, 0, 0} and usize. */
 int afm_rebalance_f64(afm_ctx* ctx, int64_t T, int64_t A, int64_t lda, const int32_t* dates,
                       int64_t nd, const double* pred, const uint64_t* trad_bits,
                       const double* hist, const uint64_t* hist_bits, int64_t h_t0, int64_t h_t1,
@@ -219,7 +223,9 @@ int afm_rebalance_f64(afm_ctx* ctx, int64_t T, int64_t A, int64_t lda, const int
                       double lo, double hi, int32_t* k_out, int32_t* books, double* weights,
                       double* sums, int32_t* upos, int64_t* usize, int32_t* status);
 /* Value / turnover recursion over the nd rebalance dates (KKT:864-892): value[nd+1] (value[0] =
- * v0), turnover[nd], long_ret[nd], short_ret[nd]. */
+ * v0), turnover[nd], long_ret[nd], short_ret[nd].  A name in both books of a date (both selection
+ * thresholds inside one tie) holds the short position, as in the reference, which assigns the
+ * short book last (KKT:881-882), and is one term of the turnover. */
 int afm_pnl_scan_f64(afm_ctx* ctx, int64_t nd, const int32_t* k_out, const int32_t* books,
                      const double* sums, const int32_t* upos, const int64_t* usize, double v0,
                      double rate, double* value, double* turnover, double* long_ret,
@@ -230,7 +236,11 @@ int afm_pnl_scan_f64(afm_ctx* ctx, int64_t nd, const int32_t* k_out, const int32
  * afm_pnl_scan_f64 (KKT:864-892) over its steps, with the turnover aligned on the union of the
  * previous and current step's prediction sets (pred [T][lda], dates as passed to
  * afm_rebalance_f64).  value [npaths][steps+1], turnover / long_ret / short_ret
- * [npaths][steps]. */
+ * [npaths][steps].
+ * This call takes no A: every one of the lda columns of a rebalance date's pred row counts as an
+ * id of that date's prediction set when it is not NaN, whereas afm_rebalance_f64 reads the columns
+ * below A only.  The pad columns [A, lda) of pred must therefore be NaN here; a finite pad value
+ * enters the unions and shifts the members' positions away from those of afm_rebalance_f64. */
 int afm_bootstrap_pnl_f64(afm_ctx* ctx, int64_t lda, const int32_t* dates, int64_t nd,
                           const double* pred, const int32_t* k_out, const int32_t* books,
                           const double* sums, int64_t npaths, int64_t steps, const int32_t* path,
