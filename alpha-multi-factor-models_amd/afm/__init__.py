@@ -18,6 +18,8 @@ Drop-in Python surface (same names, arguments and results as the reference):
                                                     of the columns (``rolling`` over the ICs)
 * ``factor_turnover(df, prices, lags=(1, 5, 21))``  -- the rank autocorrelation and the layer /
                                                     top-10 turnover of every column
+* ``GBTRegressor(**params).fit/predict``           -- KKT:481-576 (XGBoost: boosted regression
+                                                    trees, bit-reproducible histograms)
 * ``PortfolioManager(...)``                       -- KKT:795-970
 * ``split_zscore(all_df)``                       -- KKT:424-458 (z-score + split)
 
@@ -34,6 +36,7 @@ from .screen import FactorScreen, screen_grid, select_factors  # noqa: F401
 from .xsprep import XsPrep, preprocess_factors, preprocess_grid  # noqa: F401
 from .combine import ICWeights, combine_factors, combine_grid, ic_weights  # noqa: F401
 from .turnover import Turnover, factor_turnover, turnover_grid  # noqa: F401
+from .gbt import GBTModel, GBTParams, GBTRegressor  # noqa: F401
 from .portfolio import PortfolioManager, mean_variance_weights  # noqa: F401
 from .zscore import split_zscore, zscore_grid  # noqa: F401
 
@@ -42,4 +45,5 @@ __all__ = ["compute_factors", "factor_panel", "FACTOR_NAMES", "PanelGrid", "pack
            "cross_sectional_ols", "AlphaSignalAnalyzer", "FactorScreen", "screen_grid",
            "select_factors", "PortfolioManager", "split_zscore", "zscore_grid", "XsPrep",
            "preprocess_factors", "preprocess_grid", "ICWeights", "ic_weights", "combine_grid",
-           "combine_factors", "Turnover", "turnover_grid", "factor_turnover"]
+           "combine_factors", "Turnover", "turnover_grid", "factor_turnover", "GBTParams",
+           "GBTModel", "GBTRegressor"]

@@ -1167,6 +1167,107 @@ class Pipeline:
                    year0=r["year0"], features=names)
         return out
 
+    def _gbt_rows(self, t1):
+        """(rows_t, rows_a) int32: the z-score rows of the dates [0, t1), date-major."""
+        import torch
+        bits = self.zrows                                                # [nch][lda]
+        sh = torch.arange(64, device=bits.device, dtype=torch.int64)
+        m = ((bits[:, None, :] >> sh[None, :, None]) & 1).reshape(-1, bits.shape[1])[:t1]
+        idx = torch.nonzero(m)
+        return idx[:, 0].to(torch.int32).contiguous(), idx[:, 1].to(torch.int32).contiguous()
+
+    def gbt_fit(self, params=None, *, rows: str = "train"):
+        """Boosted regression trees (``afm.gbt``) on the last ``step()``'s panel (one GPU): the
+        reference's XGBoost fits on the z-scored design.  The z statistics are the train window's
+        and z is computed where it is read; the rows are the z-score rows (``zrows``); the label
+        is the target plane.
+
+        ``rows="train"`` (KKT:499-513): the dates [0, tr1) train (weight 1) and the valid dates
+        not in train are scored every round (weight 0) -- ``model.evals`` and ``best_round``.
+        ``rows="train+valid"`` (KKT:644-652): the dates [0, v1) train, train_end's rows twice
+        where the reference's inclusive slices count that date twice (``Split.dup``).
+
+        Runs on the caller's stream.  Returns a ``GBTModel``; the device results of the fit stay
+        in ``self.gbt`` (``F``, the row lists ``rows_t`` / ``rows_a``, ``w``, ``bins``, ...)."""
+        import torch
+        from .gbt import GBTModel, _check_params, fit_device
+        if self.W > 1:
+            raise NotImplementedError("gbt_fit() runs on one GPU (world = 1)")
+        params = _check_params(params)
+        if rows not in ("train", "train+valid"):
+            raise ValueError(f"rows={rows!r}: expected 'train' or 'train+valid'")
+        if not self._stepped:
+            raise ValueError("gbt_fit(): run step() first (the panel is empty)")
+        sp, T, lda, dev = self.sp, self.T, self.lda, self.out.device
+        with self.ctx.on(torch.cuda.current_stream(dev)):                    # the caller's stream
+            rt, ra = self._gbt_rows(sp.v1)
+            n = int(rt.numel())
+            if n == 0:
+                raise ValueError("gbt_fit(): the split has no z-score rows")
+            if rows == "train":
+                w = (rt < sp.tr1).to(torch.int32)
+            else:
+                w = torch.ones(n, dtype=torch.int32, device=dev)
+                if sp.dup:
+                    w += (rt == sp.tr1 - 1).to(torch.int32)
+            y = torch.empty(n, dtype=torch.float64, device=dev)
+            tcol = torch.tensor([TARGET], dtype=torch.int32, device=dev)
+            self.ctx.call("afm_gbt_values_f64", self.out, T * lda, T, lda, tcol, 0, None, rt, ra,
+                          n, y)
+            ok = torch.isfinite(y)
+            if not bool(ok.all()):                   # a row without a label neither trains nor scores
+                rt, ra, w, y = rt[ok].contiguous(), ra[ok].contiguous(), w[ok].contiguous(), y[ok]
+                n = int(rt.numel())
+            res = fit_device(self.out, self.feat, y, w, params, T=T, lda=lda, n=n, zs=self.zs,
+                             rows_t=rt, rows_a=ra, col_stride=T * lda)
+            res.update(rows_t=rt, rows_a=ra, w=w, y=y)
+            self.gbt = res
+            return GBTModel.from_device(res, params, self.features)
+
+    def gbt_predict(self, model, n_trees=None, frame: bool = False):
+        """The trees of ``model`` (the first ``n_trees``; default all) walked over the test dates'
+        z-score rows of the resident panel: a device plane [T][lda] shaped like ``pipe.pred`` --
+        the prediction on those rows, NaN everywhere else.  ``frame=True``: the (date, id)-indexed
+        one-column frame ('pred') that ``afm.AlphaSignalAnalyzer`` and ``afm.PortfolioManager``
+        take (KKT:575, 991)."""
+        import torch
+        from .gbt import GBTModel, _n_trees
+        if self.W > 1:
+            raise NotImplementedError("gbt_predict() runs on one GPU (world = 1)")
+        if not isinstance(model, GBTModel):
+            raise TypeError(f"model: expected a GBTModel, got {type(model).__name__}")
+        if list(model.features) != list(self.features):
+            raise ValueError("gbt_predict(): the model was fit on other features than this "
+                             "pipeline's")
+        if not self._stepped:
+            raise ValueError("gbt_predict(): run step() first (the panel is empty)")
+        sp, T, lda, dev = self.sp, self.T, self.lda, self.out.device
+        pred = torch.full((T, lda), float("nan"), dtype=torch.float64, device=dev)
+        feat, thr, val = model.device_trees(dev)
+        with self.ctx.on(torch.cuda.current_stream(dev)):
+            self.ctx.call("afm_gbt_predict_f64", self.out, T * lda, lda, sp.s0, T - sp.s0,
+                          self.feat, self.p, self.zs, feat, thr, val, model.params.max_depth,
+                          _n_trees(model, n_trees), model.params.base_score, self.zrows, pred)
+        if not frame:
+            return pred
+        import pandas as pd
+        h = pred[:, :self.A].cpu().numpy()
+        t, a = np.nonzero(~np.isnan(h))
+        idx = pd.MultiIndex.from_arrays([np.asarray(self.full.dates)[t],
+                                         np.asarray(self.full.ids)[a]], names=["date", "id"])
+        return pd.DataFrame({"pred": h[t, a]}, index=idx)
+
+    def selected_features(self, model, k: int = 10) -> list:
+        """The reference's ``selected_features`` (KKT:545-554, 637): the ``k`` most-split columns
+        of ``model`` united with the columns the step's Lasso kept, in ``FEATURES`` order."""
+        if self.W > 1:
+            raise NotImplementedError("selected_features() runs on one GPU (world = 1)")
+        if not self._stepped:
+            raise ValueError("selected_features(): run step() first (no Lasso fit)")
+        beta = self.lasso_beta.cpu().numpy()
+        keep = set(model.top_features(k)) | {f for f, b in zip(self.features, beta[1:]) if b != 0}
+        return [f for f in self.features if f in keep]
+
     def summary(self) -> dict:
         """Host copies of the headline results (after a synchronize)."""
         v = self.pnl["value"].cpu().numpy()

@@ -91,6 +91,9 @@ int afm_ctx_set_option(afm_ctx* ctx, const char* name, int64_t value) {
         ctx->factor_fast = value != 0;
     } else if (n == "gram_checked") {
         ctx->gram_checked = value != 0;
+    } else if (n == "gbt_rows_per_wg") {
+        AFM_CHECK_ARG(value >= 0 && value <= (1 << 20), "gbt_rows_per_wg: 0 (auto) or 1..2^20 rows");
+        ctx->gbt_rows_per_wg = value;
     } else {
         AFM_CHECK_ARG(false, "unknown option " + n);
     }
@@ -105,6 +108,7 @@ int afm_ctx_get_option(afm_ctx* ctx, const char* name, int64_t* value) {
     else if (n == "factor_pair") *value = ctx->factor_pair ? 1 : 0;
     else if (n == "factor_fast") *value = ctx->factor_fast ? 1 : 0;
     else if (n == "gram_checked") *value = ctx->gram_checked ? 1 : 0;
+    else if (n == "gbt_rows_per_wg") *value = ctx->gbt_rows_per_wg;
     else AFM_CHECK_ARG(false, "unknown option " + n);
     return AFM_OK;
 }
