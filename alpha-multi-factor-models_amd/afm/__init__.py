@@ -37,6 +37,7 @@ from .xsprep import XsPrep, preprocess_factors, preprocess_grid  # noqa: F401
 from .combine import ICWeights, combine_factors, combine_grid, ic_weights  # noqa: F401
 from .turnover import Turnover, factor_turnover, turnover_grid  # noqa: F401
 from .gbt import GBTModel, GBTParams, GBTRegressor  # noqa: F401
+from .mlp import MLPModel, MLPParams, MLPRegressor  # noqa: F401
 from .portfolio import PortfolioManager, mean_variance_weights  # noqa: F401
 from .zscore import split_zscore, zscore_grid  # noqa: F401
 
@@ -46,4 +47,4 @@ __all__ = ["compute_factors", "factor_panel", "FACTOR_NAMES", "PanelGrid", "pack
            "select_factors", "PortfolioManager", "split_zscore", "zscore_grid", "XsPrep",
            "preprocess_factors", "preprocess_grid", "ICWeights", "ic_weights", "combine_grid",
            "combine_factors", "Turnover", "turnover_grid", "factor_turnover", "GBTParams",
-           "GBTModel", "GBTRegressor"]
+           "GBTModel", "GBTRegressor", "MLPParams", "MLPModel", "MLPRegressor"]

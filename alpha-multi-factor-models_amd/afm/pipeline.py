@@ -1268,6 +1268,118 @@ class Pipeline:
         keep = set(model.top_features(k)) | {f for f, b in zip(self.features, beta[1:]) if b != 0}
         return [f for f in self.features if f in keep]
 
+    def _mlp_columns(self, features):
+        """The indices into ``self.features`` of the named columns (default: all)."""
+        if features is None:
+            return list(range(len(self.features)))
+        if isinstance(features, (str, bytes)):
+            raise TypeError("features: expected a list of column names")
+        features = [str(f) for f in features]
+        unknown = [f for f in features if f not in self.features]
+        if unknown:
+            raise ValueError(f"unknown features {unknown}: not among this pipeline's")
+        if not features or len(set(features)) != len(features):
+            raise ValueError("features: expected distinct column names, at least one")
+        return [self.features.index(f) for f in features]
+
+    def _mlp_planes(self, idx, rt, ra, n_pad):
+        """The z-scored design of the rows (rt, ra) as planes [len(idx)][n_pad], zero padded: one
+        afm_gbt_values_f64 per column, at the column's own index in ``self.feat`` / ``self.zs``."""
+        import torch
+        T, lda, n = self.T, self.lda, int(rt.numel())
+        X = torch.zeros((len(idx), n_pad), dtype=torch.float64, device=self.out.device)
+        for j, k in enumerate(idx):
+            self.ctx.call("afm_gbt_values_f64", self.out, T * lda, T, lda, self.feat, k, self.zs,
+                          rt, ra, n, X[j])
+        return X
+
+    def mlp_fit(self, params=None, *, features=None):
+        """An ensemble of small dense networks (``afm.mlp``) on the last ``step()``'s panel (one
+        GPU): the reference's Dense(128) -> Dense(32) -> Dense(1) fit (KKT:668-684) on the z-scored
+        design.  The rows of the dates [0, tr1) train, date-major and unshuffled; the rows of the
+        dates [tr1 - dup, v1) are scored at the end of every epoch -- the reference's ``df_valid``
+        starts on train_end itself (``Split.dup``); rows without a finite label are dropped.
+        ``features``: the columns to fit on (default: all of ``self.features``); the reference's
+        call is ``pipe.mlp_fit(features=pipe.selected_features(gbt_model))``.
+
+        Runs on the caller's stream.  Returns a ``MLPModel``; the device results of the fit stay
+        in ``self.mlp`` (``theta``, ``evals``, ``snaps``, ``X``, ``y``, the row lists ``rows_t`` /
+        ``rows_a``, ``n_train``, ``n_eval``)."""
+        import torch
+        from .mlp import MLPModel, _check_params, _check_shape, fit_device
+        if self.W > 1:
+            raise NotImplementedError("mlp_fit() runs on one GPU (world = 1)")
+        params = _check_params(params)
+        if not self._stepped:
+            raise ValueError("mlp_fit(): run step() first (the panel is empty)")
+        idx = self._mlp_columns(features)
+        _check_shape(len(idx), params.hidden)
+        sp, T, lda, dev = self.sp, self.T, self.lda, self.out.device
+        with self.ctx.on(torch.cuda.current_stream(dev)):                    # the caller's stream
+            rt, ra = self._gbt_rows(sp.v1)
+            ev = rt >= sp.tr1 - int(bool(sp.dup))
+            tr = rt < sp.tr1
+            rt = torch.cat([rt[tr], rt[ev]]).contiguous()
+            ra = torch.cat([ra[tr], ra[ev]]).contiguous()
+            n_train, n = int(tr.sum()), int(rt.numel())
+            y = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+            tcol = torch.tensor([TARGET], dtype=torch.int32, device=dev)
+            if n:
+                self.ctx.call("afm_gbt_values_f64", self.out, T * lda, T, lda, tcol, 0, None, rt,
+                              ra, n, y)
+            ok = torch.isfinite(y[:n])
+            if not bool(ok.all()):                   # a row without a label neither trains nor scores
+                n_train = int(ok[:n_train].sum())
+                rt, ra, y = rt[ok].contiguous(), ra[ok].contiguous(), y[:n][ok]
+                n = int(rt.numel())
+            if n_train == 0:
+                raise ValueError("mlp_fit(): the split has no z-score rows to train on")
+            n_pad = (n + 63) // 64 * 64
+            X = self._mlp_planes(idx, rt, ra, n_pad)
+            yp = torch.zeros(n_pad, dtype=torch.float64, device=dev)
+            yp[:n] = y[:n]
+            res = fit_device(X, yp, n_train, n - n_train, params)
+            res.update(rows_t=rt, rows_a=ra, X=X, y=yp, n_train=n_train, n_eval=n - n_train)
+            self.mlp = res
+            return MLPModel.from_device(res, params, [self.features[k] for k in idx])
+
+    def mlp_predict(self, model, frame: bool = False, member=None):
+        """The networks of ``model`` over the test dates' z-score rows of the resident panel: a
+        device plane [T][lda] shaped like ``pipe.pred`` -- the mean over the members (default) or
+        the prediction of ``member`` on those rows, NaN everywhere else.  ``frame=True``: the
+        (date, id)-indexed one-column frame ('pred') that ``afm.AlphaSignalAnalyzer`` and
+        ``afm.PortfolioManager`` take (KKT:686-706)."""
+        import torch
+        from .mlp import MLPModel, _member, forward_device
+        if self.W > 1:
+            raise NotImplementedError("mlp_predict() runs on one GPU (world = 1)")
+        if not isinstance(model, MLPModel):
+            raise TypeError(f"model: expected a MLPModel, got {type(model).__name__}")
+        if not self._stepped:
+            raise ValueError("mlp_predict(): run step() first (the panel is empty)")
+        idx = self._mlp_columns(model.features)
+        member = _member(model, member)
+        sp, T, lda, dev = self.sp, self.T, self.lda, self.out.device
+        pred = torch.full((T, lda), float("nan"), dtype=torch.float64, device=dev)
+        with self.ctx.on(torch.cuda.current_stream(dev)):
+            rt, ra = self._gbt_rows(T)
+            te = rt >= sp.s0
+            rt, ra = rt[te].contiguous(), ra[te].contiguous()
+            n = int(rt.numel())
+            if n:
+                X = self._mlp_planes(idx, rt, ra, (n + 63) // 64 * 64)
+                out = forward_device(X, model.device_theta(dev), model.params.hidden, 0, n)
+                val = out[member, :n] if member is not None else out[:, :n].mean(dim=0)
+                pred[rt.long(), ra.long()] = val
+        if not frame:
+            return pred
+        import pandas as pd
+        h = pred[:, :self.A].cpu().numpy()
+        t, a = np.nonzero(~np.isnan(h))
+        idx = pd.MultiIndex.from_arrays([np.asarray(self.full.dates)[t],
+                                         np.asarray(self.full.ids)[a]], names=["date", "id"])
+        return pd.DataFrame({"pred": h[t, a]}, index=idx)
+
     def summary(self) -> dict:
         """Host copies of the headline results (after a synchronize)."""
         v = self.pnl["value"].cpu().numpy()

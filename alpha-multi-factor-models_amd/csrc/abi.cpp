@@ -94,6 +94,10 @@ int afm_ctx_set_option(afm_ctx* ctx, const char* name, int64_t value) {
     } else if (n == "gbt_rows_per_wg") {
         AFM_CHECK_ARG(value >= 0 && value <= (1 << 20), "gbt_rows_per_wg: 0 (auto) or 1..2^20 rows");
         ctx->gbt_rows_per_wg = value;
+    } else if (n == "mlp_steps_per_launch") {
+        AFM_CHECK_ARG(value >= 0 && value <= (1 << 20),
+                      "mlp_steps_per_launch: 0 (auto) or 1..2^20 steps");
+        ctx->mlp_steps_per_launch = value;
     } else {
         AFM_CHECK_ARG(false, "unknown option " + n);
     }
@@ -109,6 +113,7 @@ int afm_ctx_get_option(afm_ctx* ctx, const char* name, int64_t* value) {
     else if (n == "factor_fast") *value = ctx->factor_fast ? 1 : 0;
     else if (n == "gram_checked") *value = ctx->gram_checked ? 1 : 0;
     else if (n == "gbt_rows_per_wg") *value = ctx->gbt_rows_per_wg;
+    else if (n == "mlp_steps_per_launch") *value = ctx->mlp_steps_per_launch;
     else AFM_CHECK_ARG(false, "unknown option " + n);
     return AFM_OK;
 }

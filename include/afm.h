@@ -50,7 +50,9 @@ int afm_ctx_set_stream(afm_ctx* ctx, void* stream);
  *   "factor_fast"   1 (default) | 0: the clean-window fast step of the factor kernel
  *   "gram_checked"  0 (default) | 1: afm_xs_gram_f64 stages every row checked (no FAST + REDO)
  *   "gbt_rows_per_wg"  0 (default: the library's choice) | 1..2^20: rows of the chunk a workgroup
- *                   of the boosted trees' histogram kernel owns (afm_gbt.h), rounded up to 4 */
+ *                   of the boosted trees' histogram kernel owns (afm_gbt.h), rounded up to 4
+ *   "mlp_steps_per_launch"  0 (default: the library's choice) | 1..2^20: batch steps of every
+ *                   model that one launch of the network fit runs (afm_mlp.h) */
 int afm_ctx_set_option(afm_ctx* ctx, const char* name, int64_t value);
 /* The current value of an option of afm_ctx_set_option (value: out). */
 int afm_ctx_get_option(afm_ctx* ctx, const char* name, int64_t* value);
