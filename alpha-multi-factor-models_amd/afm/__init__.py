@@ -19,7 +19,9 @@ Drop-in Python surface (same names, arguments and results as the reference):
 * ``factor_turnover(df, prices, lags=(1, 5, 21))``  -- the rank autocorrelation and the layer /
                                                     top-10 turnover of every column
 * ``GBTRegressor(**params).fit/predict``           -- KKT:481-576 (XGBoost: boosted regression
-                                                    trees, bit-reproducible histograms)
+                                                    trees, bit-reproducible histograms);
+                                                    ``predict(X, pred_contribs=True)``: the exact
+                                                    TreeSHAP contributions, the bias last
 * ``PortfolioManager(...)``                       -- KKT:795-970
 * ``split_zscore(all_df)``                       -- KKT:424-458 (z-score + split)
 

@@ -9,6 +9,13 @@ the work split; ``tests/gbt_ref.py`` restates the algorithm in numpy.
 ``Pipeline.gbt_fit`` calls on the resident panel), ``GBTModel`` holds the fitted trees on the host
 and ``GBTRegressor`` is the frame / array interface.
 
+Attribution (csrc/gbt_shap.hip, include/afm_gbt_shap.h): a fit also stores the ``cover`` of every
+node (the sum of the weights of the training rows that reach it), ``contribs_dense`` /
+``GBTRegressor.predict(pred_contribs=True)`` give the exact path-dependent TreeSHAP contributions
+of every column to every prediction (XGBoost's layout: ``[n][p + 1]``, the bias last) and
+``Pipeline.gbt_contribs`` their per-date means on the resident panel; ``tests/gbt_shap_ref.py``
+restates them in numpy.
+
 Out of scope: the multi-GPU pipeline; objectives other than squared error; column / row
 subsampling; missing values (the rows are the z-score rows: every value is finite); early
 stopping inside the fit (``best_round`` names the round of highest validation IC afterwards, and
@@ -130,7 +137,8 @@ def fit_device(base, cols, y, w, params: GBTParams, *, T: int, lda: int, n: int,
     rows_a[i]) of the planes base + cols[k] * col_stride ([T][lda]; None: date 0 / asset i),
     z-scored with ``zs`` where given; ``y`` float64 [n], ``w`` int32 [n] (0 = evaluated only).
     Returns device tensors: cuts, ncuts, bins [p][n_pad], feat / bin / thr / val [n_rounds][nn],
-    F [n] and evals [n_rounds][2][6].  Nothing synchronises the host after the cuts."""
+    F [n], evals [n_rounds][2][6] and cover [n_rounds][nn] int64 (the sum of w over the rows that
+    reach each node: the fit's H).  Nothing synchronises the host after the cuts."""
     import torch
     params = _check_params(params)
     dev = base.device
@@ -161,6 +169,8 @@ def fit_device(base, cols, y, w, params: GBTParams, *, T: int, lda: int, n: int,
     ctx.call("afm_gbt_fit_f64", bins, n, n_pad, p, cuts, ncuts, y, w, R, D, B, params.eta,
              params.reg_lambda, params.gamma, params.min_child_weight, res["feat"], res["bin"],
              res["thr"], res["val"], res["F"], res["evals"], scr)
+    res["cover"] = torch.empty((R, nn), dtype=torch.int64, device=dev)
+    ctx.call("afm_gbt_cover_i64", bins, n, n_pad, p, w, res["feat"], res["bin"], D, R, res["cover"])
     if bufs is not None:
         bufs["gbt_scratch"] = scr
     return res
@@ -169,30 +179,37 @@ def fit_device(base, cols, y, w, params: GBTParams, *, T: int, lda: int, n: int,
 class GBTModel:
     """A fitted ensemble on the host: the tree arrays ``feat`` / ``bin`` / ``thr`` / ``val``
     [n_rounds][nn] in heap order (``feat`` >= 0: the split column, -1: a leaf, -2: absent),
-    ``cuts`` / ``ncuts``, ``params``, ``features`` (column names),
+    ``cuts`` / ``ncuts``, ``params``, ``features`` (column names), ``cover`` (int64 [n_rounds][nn],
+    the sum of the training weights that reach each node; None on a model saved without it),
     ``evals`` (a frame per round: rmse and IC of the rows that train and of those only evaluated)
     and ``best_round`` (1-based: the round of highest validation IC, the last round when there is
     no validation row)."""
 
-    def __init__(self, params: GBTParams, features, feat, bin, thr, val, cuts, ncuts, evals_raw):
+    def __init__(self, params: GBTParams, features, feat, bin, thr, val, cuts, ncuts, evals_raw,
+                 cover=None):
         self.params = params
         self.features = [str(f) for f in features]
         self.feat, self.bin = np.asarray(feat, np.int32), np.asarray(bin, np.int32)
         self.thr, self.val = np.asarray(thr, np.float64), np.asarray(val, np.float64)
         self.cuts, self.ncuts = np.asarray(cuts, np.float64), np.asarray(ncuts, np.int32)
         self.evals_raw = np.asarray(evals_raw, np.float64)
+        self.cover = None if cover is None else np.asarray(cover, np.int64)
+        if self.cover is not None and self.cover.shape != self.feat.shape:
+            raise ValueError(f"cover: expected shape {self.feat.shape}, got {self.cover.shape}")
         self.evals = evals_frame(self.evals_raw)
         ic = self.evals["valid_ic"].to_numpy()
         self.best_round = (int(np.nanargmax(ic)) + 1 if np.isfinite(ic).any()
                            else len(self.feat))
         self._dev = None
+        self._dev_cover = None
 
     @classmethod
     def from_device(cls, res: dict, params: GBTParams, features) -> "GBTModel":
         h = {k: res[k].cpu().numpy() for k in ("feat", "bin", "thr", "val", "cuts", "ncuts",
                                                "evals")}
+        cover = res["cover"].cpu().numpy() if "cover" in res else None
         return cls(params, features, h["feat"], h["bin"], h["thr"], h["val"], h["cuts"],
-                   h["ncuts"], h["evals"])
+                   h["ncuts"], h["evals"], cover=cover)
 
     @property
     def n_trees(self) -> int:
@@ -206,18 +223,39 @@ class GBTModel:
                                        for a in (self.feat, self.thr, self.val)))
         return self._dev[1]
 
+    def device_cover(self, device):
+        """``cover`` on ``device`` (cached); ValueError when the model has none."""
+        import torch
+        if self.cover is None:
+            raise ValueError("the model has no cover (saved before the fit stored it): refit it")
+        if self._dev_cover is None or self._dev_cover[0] != device:
+            self._dev_cover = (device,
+                               torch.from_numpy(np.ascontiguousarray(self.cover)).to(device))
+        return self._dev_cover[1]
+
     def importance(self, kind: str = "weight") -> np.ndarray:
         """Per column: 'weight' = the number of splits on it (XGBoost's get_score default, the
         count the reference ranks by, KKT:548); 'gain' = the mean decrease of the leaf values'
         spread, |val[left] - val[right]| averaged over its splits (a proxy on the stored arrays:
-        the split gains themselves are not kept)."""
+        the split gains themselves are not kept); 'cover' / 'total_cover' = the mean / the sum of
+        the cover of its splits (XGBoost's names; ValueError on a model without ``cover``)."""
         p = len(self.features)
         split = self.feat >= 0
         cnt = np.bincount(self.feat[split], minlength=p).astype(np.float64)
         if kind == "weight":
             return cnt
+        if kind in ("cover", "total_cover"):
+            if self.cover is None:
+                raise ValueError(f"kind={kind!r}: the model has no cover")
+            tot = np.bincount(self.feat[split], weights=self.cover[split].astype(np.float64),
+                              minlength=p)
+            if kind == "total_cover":
+                return tot
+            with np.errstate(all="ignore"):
+                return np.where(cnt > 0, tot / cnt, 0.0)
         if kind != "gain":
-            raise ValueError(f"kind={kind!r}: expected 'weight' or 'gain'")
+            raise ValueError(f"kind={kind!r}: expected 'weight', 'gain', 'cover' or "
+                             f"'total_cover'")
         r, v = np.nonzero(split)
         d = np.abs(self.val[r, 2 * v + 1] - self.val[r, 2 * v + 2])
         tot = np.bincount(self.feat[split], weights=d, minlength=p)
@@ -232,8 +270,9 @@ class GBTModel:
         return [self.features[j] for j in order[:k] if cnt[j] > 0]
 
     def save(self, path):
-        np.savez(path, feat=self.feat, bin=self.bin, thr=self.thr, val=self.val, cuts=self.cuts,
-                 ncuts=self.ncuts, evals=self.evals_raw,
+        extra = {} if self.cover is None else {"cover": self.cover}
+        np.savez(path, **extra, feat=self.feat, bin=self.bin, thr=self.thr, val=self.val,
+                 cuts=self.cuts, ncuts=self.ncuts, evals=self.evals_raw,
                  features=np.asarray(self.features, dtype=str),
                  params_names=np.asarray(list(asdict(self.params)), dtype=str),
                  params_values=np.asarray(list(asdict(self.params).values()), dtype=np.float64))
@@ -245,7 +284,8 @@ class GBTModel:
             for name in ("n_rounds", "max_depth", "max_bin"):
                 kw[name] = int(kw[name])
             return cls(GBTParams(**kw), z["features"].tolist(), z["feat"], z["bin"], z["thr"],
-                       z["val"], z["cuts"], z["ncuts"], z["evals"])
+                       z["val"], z["cuts"], z["ncuts"], z["evals"],
+                       cover=z["cover"] if "cover" in z.files else None)
 
 
 def _host_matrix(X):
@@ -349,7 +389,11 @@ class GBTRegressor:
         cnt = self.model_.importance("weight")
         return cnt / cnt.sum() if cnt.sum() > 0 else cnt
 
-    def predict(self, X, n_trees=None):
+    def predict(self, X, n_trees=None, pred_contribs=False):
+        """The prediction [n]; ``pred_contribs=True``: the TreeSHAP contributions [n][p + 1], the
+        bias last (``contribs_dense``)."""
+        if pred_contribs:
+            return contribs_dense(self.model_, X, n_trees)
         return predict_dense(self.model_, X, n_trees)
 
 
@@ -379,3 +423,63 @@ def predict_dense(model: GBTModel, X, n_trees=None) -> np.ndarray:
     _lib.run("afm_gbt_predict_f64", base, lda, lda, 0, 1, cols, p, None, feat, thr, val,
              model.params.max_depth, _n_trees(model, n_trees), model.params.base_score, bits, pred)
     return pred[0, :n].cpu().numpy()
+
+
+def check_cover(model: GBTModel, n_trees=None):
+    """What the contributions need of ``model.cover``, checked on the host: it is there, every
+    present node of the first ``n_trees`` trees has cover >= 1, and a split's cover is the sum of
+    its children's.  ValueError otherwise."""
+    if model.cover is None:
+        raise ValueError("the model has no cover (saved before the fit stored it): the "
+                         "contributions need the cover of every node -- refit it")
+    R = _n_trees(model, n_trees)
+    feat, cover = model.feat[:R], model.cover[:R]
+    if (cover[feat != ABSENT] < 1).any():
+        raise ValueError("cover: a present node has cover < 1")
+    r, v = np.nonzero(feat >= 0)
+    if (cover[r, v] != cover[r, 2 * v + 1] + cover[r, 2 * v + 2]).any():
+        raise ValueError("cover: a split's cover is not the sum of its children's")
+
+
+def shap_device(ctx, model: GBTModel, n_trees, base, col_stride, lda, t0, nt, cols, p, zs, bits,
+                *, contrib: bool, agg: bool) -> dict:
+    """afm_gbt_shap_f64 on device buffers, on the context's stream: ``contrib`` [nt][p+1][lda]
+    and / or ``agg`` [nt][p+1][2] with ``cnt`` [nt] (include/afm_gbt_shap.h)."""
+    import torch
+    dev = base.device
+    feat, thr, val = model.device_trees(dev)
+    cover = model.device_cover(dev)
+    D = model.params.max_depth
+    nbytes = ctx.call("afm_gbt_shap_scratch_bytes", lda, nt, p, D, n_trees)
+    scr = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    out = {"contrib": torch.empty((nt, p + 1, lda), dtype=torch.float64, device=dev)
+           if contrib else None,
+           "agg": torch.empty((nt, p + 1, 2), dtype=torch.float64, device=dev) if agg else None,
+           "cnt": torch.empty(nt, dtype=torch.int64, device=dev) if agg else None}
+    ctx.call("afm_gbt_shap_f64", base, col_stride, lda, t0, nt, cols, p, zs, feat, thr, val, cover,
+             D, n_trees, model.params.base_score, bits, scr, out["contrib"], out["agg"],
+             out["cnt"])
+    return out
+
+
+def contribs_dense(model: GBTModel, X, n_trees=None) -> np.ndarray:
+    """The exact path-dependent TreeSHAP contributions of the first ``n_trees`` trees (default:
+    all) on the rows of X -> host [n][p + 1], the bias last (XGBoost's ``pred_contribs``): each
+    row sums to the prediction up to rounding."""
+    import torch
+    Xh, _ = _host_matrix(X)
+    n, p = Xh.shape
+    if p != len(model.features):
+        raise ValueError(f"X has {p} features, model was fit with {len(model.features)}")
+    R = _n_trees(model, n_trees)
+    check_cover(model, R)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    base, lda = _dense_planes(Xh, dev)
+    bits = torch.zeros((1, lda), dtype=torch.int64, device=dev)
+    bits[0, :n] = 1
+    cols = torch.arange(p, dtype=torch.int32, device=dev)
+    ctx = _lib.Context.get(dev.index)
+    ctx.bind_stream()
+    out = shap_device(ctx, model, R, base, lda, lda, 0, 1, cols, p, None, bits, contrib=True,
+                      agg=False)
+    return np.ascontiguousarray(out["contrib"][0, :, :n].T.cpu().numpy())

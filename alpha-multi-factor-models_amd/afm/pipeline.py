@@ -1257,15 +1257,78 @@ class Pipeline:
                                          np.asarray(self.full.ids)[a]], names=["date", "id"])
         return pd.DataFrame({"pred": h[t, a]}, index=idx)
 
-    def selected_features(self, model, k: int = 10) -> list:
+    def gbt_contribs(self, model, n_trees=None, *, split: str = "test", rows: bool = False):
+        """What the predictions of ``model`` (its first ``n_trees`` trees; default all) are made
+        of on the z-score rows of a split of the resident panel (one GPU): the exact
+        path-dependent TreeSHAP contributions (``afm.gbt``, include/afm_gbt_shap.h), aggregated
+        per date on the device.  ``split``: 'train' (the dates [0, tr1)), 'valid' (the valid
+        dates not in train, [tr1, v1)) or 'test' ([s0, T)).
+
+        Returns a dict: ``by_date`` (a frame, dates x features + 'bias': the mean |phi| over the
+        date's rows; NaN on a date without rows), ``mean_by_date`` (the same shape: the mean phi),
+        ``importance`` (a Series over the features: the mean |phi| over all rows of the split,
+        sorted descending), ``n`` (a Series: the rows per date) and, with ``rows=True``,
+        ``contrib``: the device planes [nt][p + 1][lda] (date, column with the bias last, asset;
+        NaN off the rows).  ``contrib`` takes nt * (p + 1) * lda * 8 bytes -- 4.8 GB for the 605
+        test dates of the 10,000 x 5,040 configuration with its 97 columns, about 8 GB per 1,000
+        dates -- which is why it is off by default."""
+        import pandas as pd
+        import torch
+        from .gbt import GBTModel, _n_trees, check_cover, shap_device
+        if self.W > 1:
+            raise NotImplementedError("gbt_contribs() runs on one GPU (world = 1)")
+        if not isinstance(model, GBTModel):
+            raise TypeError(f"model: expected a GBTModel, got {type(model).__name__}")
+        if split not in ("train", "valid", "test"):
+            raise ValueError(f"split={split!r}: expected 'train', 'valid' or 'test'")
+        if list(model.features) != list(self.features):
+            raise ValueError("gbt_contribs(): the model was fit on other features than this "
+                             "pipeline's")
+        if not self._stepped:
+            raise ValueError("gbt_contribs(): run step() first (the panel is empty)")
+        R = _n_trees(model, n_trees)
+        check_cover(model, R)
+        sp, T, lda, dev = self.sp, self.T, self.lda, self.out.device
+        t0, t1 = {"train": (0, sp.tr1), "valid": (sp.tr1, sp.v1), "test": (sp.s0, T)}[split]
+        if t1 <= t0:
+            raise ValueError(f"gbt_contribs(): the {split} split has no dates")
+        with self.ctx.on(torch.cuda.current_stream(dev)):
+            out = shap_device(self.ctx, model, R, self.out, T * lda, lda, t0, t1 - t0, self.feat,
+                              self.p, self.zs, self.zrows, contrib=rows, agg=True)
+            agg, cnt = out["agg"].cpu().numpy(), out["cnt"].cpu().numpy()
+        names = list(self.features) + ["bias"]
+        dates = pd.Index(np.asarray(self.full.dates)[t0:t1], name="date")
+        with np.errstate(all="ignore"):
+            per = agg / cnt[:, None, None].astype(np.float64)
+            imp = agg[:, :self.p, 1].sum(axis=0) / float(cnt.sum())
+        res = {"by_date": pd.DataFrame(per[:, :, 1], index=dates, columns=names),
+               "mean_by_date": pd.DataFrame(per[:, :, 0], index=dates, columns=names),
+               "importance": pd.Series(imp, index=list(self.features)).sort_values(
+                   ascending=False, kind="stable"),
+               "n": pd.Series(cnt, index=dates)}
+        if rows:
+            res["contrib"] = out["contrib"]
+        return res
+
+    def selected_features(self, model, k: int = 10, *, by: str = "weight",
+                          split: str = "valid") -> list:
         """The reference's ``selected_features`` (KKT:545-554, 637): the ``k`` most-split columns
-        of ``model`` united with the columns the step's Lasso kept, in ``FEATURES`` order."""
+        of ``model`` united with the columns the step's Lasso kept, in ``FEATURES`` order.
+        ``by="shap"``: the ``k`` columns of largest mean |phi| on ``split`` (``gbt_contribs``'s
+        ``importance``; columns with none are left out) in place of the most-split ones."""
         if self.W > 1:
             raise NotImplementedError("selected_features() runs on one GPU (world = 1)")
+        if by not in ("weight", "shap"):
+            raise ValueError(f"by={by!r}: expected 'weight' or 'shap'")
         if not self._stepped:
             raise ValueError("selected_features(): run step() first (no Lasso fit)")
+        if by == "shap":
+            imp = self.gbt_contribs(model, split=split)["importance"]
+            top = [f for f in imp.index[:k] if imp[f] > 0]
+        else:
+            top = model.top_features(k)
         beta = self.lasso_beta.cpu().numpy()
-        keep = set(model.top_features(k)) | {f for f, b in zip(self.features, beta[1:]) if b != 0}
+        keep = set(top) | {f for f, b in zip(self.features, beta[1:]) if b != 0}
         return [f for f in self.features if f in keep]
 
     def _mlp_columns(self, features):
