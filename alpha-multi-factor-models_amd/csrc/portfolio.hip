@@ -32,10 +32,11 @@
 
 #pragma clang fp contract(off)
 
+#include "afm_order.h"                 // okey
+
 namespace afm {
 namespace {
 
-typedef unsigned long long u64;
 constexpr int kT = 256;        // threads per workgroup
 constexpr int kMaxK = 128;     // book-size cap; the global book arrays are [nd][2][kMaxK]
 constexpr int kMaxWords = 512; // lda <= 32768 assets
@@ -74,12 +75,6 @@ struct RebArgs {
     const double* mu;         // [T][lda] expected returns, or null: the history window's mean
     double gamma;             // risk tolerance
 };
-
-__device__ __forceinline__ u64 okey(double v) {   // order-preserving key, -0.0 == +0.0
-    if (v == 0.0) v = 0.0;
-    u64 u = (u64)__double_as_longlong(v);
-    return (u >> 63) ? ~u : (u | (1ull << 63));
-}
 
 __device__ __forceinline__ bool bit_at(const uint64_t* bits, int64_t lda, int64_t t, int64_t a) {
     return (bits[(t >> 6) * lda + a] >> (t & 63)) & 1ull;

@@ -17,131 +17,40 @@
 //                       non-finite value on the date, takes the masked path: per return, pandas'
 //                       rule with up to two masked rankings (an excluded row sorts as the pad key).
 //
-// The rows of a date are sorted in runs, each a bitonic network in LDS over a power of two: runs
-// of kRankChunk rows while that many are left, then the largest power of two that fits while at
-// least 2 * kRankMinRun rows are left, then the rest padded (9,371 rows: 8192 + 1179 padded to
-// 2048, less than half the compare-exchanges of one network over 16384).  A row's bounds are the
-// sums of its bounds in every run (xs_rank_kernel's scheme).  A date of up to kRankLdsRows rows
-// keeps its runs side by side in LDS; a longer one (up to kRankMaxRows) writes each sorted run to
-// the workgroup's slot of the caller's scratch and searches there.  The grid is then capped at
-// kRankSlots workgroups, each looping over its items, so the scratch is kRankSlots * lda words.
+// The sort and the searches are afm_order.h's run sort: the rows of a date in runs, each a bitonic
+// network in LDS over a power of two (9,371 rows: 8192 + 1179 padded to 2048, less than half the
+// compare-exchanges of one network over 16384), a row's bounds the sums of its bounds in every
+// run (xs_rank_kernel's scheme).  A date of up to kRankLdsRows rows keeps its runs side by side in
+// LDS; a longer one (up to kRankMaxRows) writes each sorted run to the workgroup's slot of the
+// caller's scratch and searches there.  The grid is then capped at kRankSlots workgroups, each
+// looping over its items, so the scratch is kRankSlots * lda words.
 #include "afm_internal.h"
 #include "afm_rankic.h"
 
 #pragma clang fp contract(off)
 
 #include "afm_np_sum.h"                // qnan
+#include "afm_order.h"                 // okey, sort_rows, bounds
 
 namespace afm {
 namespace {
 
-typedef unsigned long long u64;
-typedef long long i64;
 constexpr int kRankThreads = 1024;     // 16 waves
-constexpr int kRankLdsRows = 16384;    // rows of a date sorted and searched in LDS (128 KB of keys)
-constexpr int kRankChunk = 16384;      // rows of the longest sorted run
-constexpr int kRankMinRun = 1024;      // no run is split below twice this
 constexpr int kRankMaxRows = 32768;    // afm_xs_prepare_f64's limit
 constexpr int kRankPer = kRankMaxRows / kRankThreads;   // rows per thread (masked path registers)
 constexpr int kRankSlots = 1024;       // workgroups of a launch that uses the scratch
-constexpr u64 kRankPad = ~0ull;        // above the key of every finite value and of +-inf
-static_assert(kRankChunk == kRankLdsRows && (kRankChunk & (kRankChunk - 1)) == 0 &&
-              kRankChunk % (2 * kRankMinRun) == 0, "runs sort in LDS, side by side");
+// the entry points' own limits (the scratch is needed past kRankLdsRows rows; the tests shape
+// their dates by both): afm_order.h's, restated
+constexpr int kRankLdsRows = 16384;
+constexpr int kRankChunk = 16384;
+static_assert(kRankThreads == kSortThreads, "afm_order.h's sort is written for this workgroup");
+static_assert(kRankLdsRows == kSortLdsRows && kRankChunk == kSortChunk, "afm_order.h's run sort");
 
-__device__ __forceinline__ u64 okey(double v) {          // analyzer.hip's: -0.0 ties with 0.0
-    if (v == 0.0) v = 0.0;
-    u64 u = (u64)__double_as_longlong(v);
-    return (u >> 63) ? ~u : (u | (1ull << 63));
-}
-
-__host__ __device__ __forceinline__ int pow2_at_least(int n) {
-    int p = 2;
-    while (p < n) p <<= 1;
-    return p;
-}
-
-// ascending bitonic sort of key[0, P), P a power of two; ends with a barrier
-__device__ void bitonic_sort(u64* key, int P) {
-    const int tid = threadIdx.x;
-    for (int size = 2; size <= P; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int e = tid; e < P / 2; e += kRankThreads) {
-                const int lo = 2 * e - (e & (stride - 1));
-                const int hi = lo + stride;
-                const bool up = (lo & size) == 0;
-                const u64 ka = key[lo], kb = key[hi];
-                if ((ka > kb) == up && ka != kb) {
-                    key[lo] = kb;
-                    key[hi] = ka;
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
-// rows of the next sorted run when rem > 0 rows are left (a power of two unless it is the last)
-__device__ __forceinline__ int run_rows(int rem) {
-    if (rem >= kRankChunk) return kRankChunk;
-    return rem >= 2 * kRankMinRun ? 1 << (31 - __clz(rem)) : rem;
-}
-
-// The keys keyfn(e), e in [0, n), sorted run by run: run [c0, c0 + len) at lds + c0 when n <=
-// kRankLdsRows (only the last run is padded, so the runs do not overlap), else at scr + c0.  All
-// threads call it; LDS and scr hold the result after the closing barrier.
-template <class KeyFn>
-__device__ void sort_rows(u64* lds, u64* scr, int n, KeyFn keyfn) {
-    const int tid = threadIdx.x;
-    const bool in_lds = n <= kRankLdsRows;
-    __syncthreads();                                       // the previous searches are done
-    for (int c0 = 0; c0 < n;) {
-        const int len = run_rows(n - c0);
-        const int P = pow2_at_least(len);
-        u64* buf = in_lds ? lds + c0 : lds;
-        for (int e = tid; e < P; e += kRankThreads) buf[e] = e < len ? keyfn(c0 + e) : kRankPad;
-        __syncthreads();
-        bitonic_sort(buf, P);
-        if (!in_lds) {
-            for (int e = tid; e < len; e += kRankThreads) scr[c0 + e] = buf[e];
-            __syncthreads();
-        }
-        c0 += len;
-    }
-}
-
-template <class Ptr>
-__device__ __forceinline__ int bounds_sum(Ptr K, int len, u64 k) {
-    int lo = 0, hi = len;
-    while (lo < hi) {                                      // first key >= k
-        const int m = (lo + hi) >> 1;
-        if (K[m] < k) lo = m + 1; else hi = m;
-    }
-    const int lb = lo;
-    hi = len;
-    while (lo < hi) {                                      // first key > k
-        const int m = (lo + hi) >> 1;
-        if (K[m] <= k) lo = m + 1; else hi = m;
-    }
-    return lb + lo;
-}
-
-// 2 * (average rank) of key k (< kRankPad) among the sorted keys below the pad
+// 2 * (average rank) of key k (< kSortPad) among the sorted keys below the pad
 __device__ __forceinline__ int rank2(const u64* lds, const u64* scr, int n, u64 k) {
-    int s = 1;
-    if (n <= kRankLdsRows) {
-        for (int c0 = 0; c0 < n;) {
-            const int len = run_rows(n - c0);
-            s += bounds_sum(lds + c0, len, k);
-            c0 += len;
-        }
-    } else {
-        for (int c0 = 0; c0 < n;) {
-            const int len = run_rows(n - c0);
-            s += bounds_sum(scr + c0, len, k);
-            c0 += len;
-        }
-    }
-    return s;
+    int lb, ub;
+    bounds(lds, scr, n, k, lb, ub);
+    return 1 + lb + ub;
 }
 
 // the sum of v over the workgroup (exact: integers), on every thread
@@ -302,7 +211,7 @@ __global__ __launch_bounds__(kRankThreads) void rank_ic_kernel(RankIcArgs g) {
             sort_rows(lds, scr, n, [&](int e) {
                 const double f = fval(e);
                 const bool in = own ? f == f : __builtin_isfinite(f) && __builtin_isfinite(R[e]);
-                return in ? okey(f) : kRankPad;
+                return in ? okey(f) : kSortPad;
             });
             int rx[kRankPer];                              // 0: the row is not in the pair
 #pragma unroll
@@ -318,7 +227,7 @@ __global__ __launch_bounds__(kRankThreads) void rank_ic_kernel(RankIcArgs g) {
             sort_rows(lds, scr, n, [&](int e) {
                 const double r = R[e];
                 const bool in = own ? r == r : __builtin_isfinite(r) && __builtin_isfinite(fval(e));
-                return in ? okey(r) : kRankPad;
+                return in ? okey(r) : kSortPad;
             });
             i64 sxx = 0, syy = 0, sxy = 0;
 #pragma unroll

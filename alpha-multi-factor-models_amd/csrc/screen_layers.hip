@@ -10,10 +10,10 @@
 //                                1. gather: the column's values at the date's rows (z-scored on
 //                                   the way when zs is given, screen_ic_kernel's expression) into
 //                                   register-resident order keys; a NaN value has no key.
-//                                2. select: xs_layers_kernel's radix select -- nine decile bounds
-//                                   and the 10th largest of the n_k keyed rows in the same eight
-//                                   byte passes, ties by position -- gives every row its layer
-//                                   (to LDS, one byte per row) and the top-10 rows their rank.
+//                                2. select: afm_order.h's decile select -- nine decile bounds and
+//                                   the 10th largest of the n_k keyed rows in the same eight byte
+//                                   passes, ties by position -- gives every row its layer (to
+//                                   LDS, one byte per row) and the top-10 rows their rank.
 //                                3. means: the three return planes go through LDS in chunks of
 //                                   kSlChunk rows, each chunk sorted by layer (row order kept
 //                                   inside a layer), and 30 lanes of wave 0 run xs_stats_kernel's
@@ -37,11 +37,11 @@
 #pragma clang fp contract(off)
 
 #include "afm_np_sum.h"
+#include "afm_order.h"                 // okey, decile_select
 
 namespace afm {
 namespace {
 
-typedef unsigned long long u64;
 constexpr int kSlThreads = 512;                    // threads per (date, column) workgroup
 constexpr int kSlFewKeys = 8;                      // register keys per thread, dates of few rows
 constexpr int kSlSmallKeys = 24;                   // ... of more
@@ -52,8 +52,7 @@ constexpr int kSlMaxRows = 32768;                  // lda limit (afm_xs_prepare_
 constexpr int kSlChunk = 512;                      // rows per staging chunk of the return planes
 constexpr int kSlBatch = 8;                        // gathered rows of a thread in flight together
 constexpr int kSlTopK = 10;
-constexpr int kSlLayers = 10;
-constexpr int kSlTargets = 10;                     // 9 decile bounds + the 10th largest
+constexpr int kSlLayers = kOrdLayers;
 constexpr int kSlWaves = kSlThreads / 64;
 constexpr int kSlCells = 4 * kSlTopK;              // scratch doubles per item: f, r1, r2, r5
 static_assert(kSlFewKeys * kSlThreads == kSlFewRows, "few-key select capacity");
@@ -63,16 +62,7 @@ static_assert(kSlChunk == kSlThreads, "one staged row per thread");
 static_assert(kSlFewKeys % kSlBatch == 0 && kSlSmallKeys % kSlBatch == 0 &&
                   kSlLargeKeys % kSlBatch == 0, "whole batches");
 static_assert(kSlMaxRows <= 65536, "positions are selected in two byte passes");
-
-__device__ __forceinline__ u64 okey(double v) {    // analyzer.hip's order key (-0.0 == 0.0)
-    if (v == 0.0) v = 0.0;
-    u64 u = (u64)__double_as_longlong(v);
-    return (u >> 63) ? ~u : (u | (1ull << 63));
-}
-__device__ __forceinline__ int layer_of(int r, int n) {   // KKT:328-330
-    int l = (int)((double)r / (double)n * kSlLayers) + 1;
-    return l > kSlLayers ? kSlLayers : l;
-}
+static_assert(kSlTopK == kSelTop, "the select's last target is the book's last row");
 
 struct SlArgs {
     const double* base;       // plane k: base + cols[k] * col_stride, [T][lda]
@@ -92,11 +82,7 @@ struct SlArgs {
 };
 
 struct SlSelect {
-    int hist[kSlTargets][256];
-    u64 prefix[kSlTargets];
-    int need[kSlTargets];
-    int rneed[kSlTargets];                // target rank (1-based), 0 = no row
-    int eqidx[kSlTargets];                // the position of the target row
+    DecileSelect sel;
     int nk;
     int ntop;
     int wcnt[kSlWaves][kSlLayers];        // rows of each layer in each wave's 64 rows of a chunk
@@ -105,28 +91,6 @@ struct SlSelect {
     u64 topk[kSlTopK];
     int topi[kSlTopK];
 };
-
-// The smallest digit d of a 256-bin histogram whose cumulative count reaches `need`, by one wave
-// (bins 4 * lane .. 4 * lane + 3 per lane).  True on the lane that holds d; `before` = the count
-// of the smaller digits.
-__device__ __forceinline__ bool pick_digit(const int* h, int need, int lane, int& d, int& before) {
-    const int h0 = h[4 * lane], h1 = h[4 * lane + 1], h2 = h[4 * lane + 2], h3 = h[4 * lane + 3];
-    const int s4 = h0 + h1 + h2 + h3;
-    int P = s4;                                            // inclusive prefix over lanes
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(P, o, 64);
-        if (lane >= o) P += v;
-    }
-    const u64 m = __ballot(P >= need);
-    if (!m || lane != __builtin_ctzll(m)) return false;
-    int acc = P - s4;
-    if (acc + h0 >= need) { d = 4 * lane; }
-    else if (acc + h0 + h1 >= need) { d = 4 * lane + 1; acc += h0; }
-    else if (acc + h0 + h1 + h2 >= need) { d = 4 * lane + 2; acc += h0 + h1; }
-    else { d = 4 * lane + 3; acc += h0 + h1 + h2; }
-    before = acc;
-    return true;
-}
 
 // NR: register keys per thread.  The workgroup takes the dates with lo < nrows <= NR * kSlThreads
 // (and, for lo < 0, the dates without rows).  The few-key instantiation is held to the registers
@@ -212,135 +176,20 @@ __global__ __launch_bounds__(kSlThreads, NR <= kSlFewKeys ? 4 : 2) void screen_l
         if (tid < kSlCells) cells[tid] = qnan();
         return;
     }
-    // ---- 2. select (xs_layers_kernel's, over the keyed rows) ----------------------------------
-    if (tid < kSlTargets) {
-        int r;
-        if (tid < kSlTargets - 1) {       // R_l: the largest rank with layer <= l (l = tid + 1)
-            int lo_ = 0, hi = nk;
-            while (lo_ < hi) {
-                const int m = (lo_ + hi + 1) >> 1;
-                if (layer_of(m, nk) <= tid + 1) lo_ = m; else hi = m - 1;
-            }
-            r = lo_;
-        } else {
-            r = nk >= kSlTopK ? kSlTopK : nk;              // the 10th largest (or the n_k-th)
-        }
-        sh.rneed[tid] = r;
-        sh.need[tid] = r;
-        sh.prefix[tid] = 0ull;
-        sh.eqidx[tid] = 0;
-    }
+    // ---- 2. select (afm_order.h's decile select over the keyed rows) --------------------------
     if (tid == 0) atomicMax(g.nmax + k, nk);
-    __syncthreads();
-    u64 pmask = 0ull;
-    for (int shift = 56; shift >= 0; shift -= 8) {
-        for (int e = tid; e < kSlTargets * 256; e += kSlThreads) (&sh.hist[0][0])[e] = 0;
-        __syncthreads();
-        if (shift == 56) {
-            // every target's prefix is empty: one histogram of the top digit, copied to the
-            // ascending targets and mirrored for the complemented one
-#pragma unroll
-            for (int j = 0; j < NR; ++j)
-                if ((keyed >> j) & 1) atomicAdd(&sh.hist[0][ks[j] >> 56], 1);
-            __syncthreads();
-            if (tid < 256) {
-                const int h = sh.hist[0][tid];
-#pragma unroll
-                for (int q = 1; q < kSlTargets - 1; ++q) sh.hist[q][tid] = h;
-                sh.hist[kSlTargets - 1][255 - tid] = h;
-            }
-        } else {
-            u64 pf[kSlTargets];
-            bool act[kSlTargets];
-#pragma unroll
-            for (int q = 0; q < kSlTargets; ++q) {
-                pf[q] = sh.prefix[q];
-                act[q] = sh.need[q] > 0;
-            }
-#pragma unroll
-            for (int j = 0; j < NR; ++j) {
-                if ((keyed >> j) & 1) {
-#pragma unroll
-                    for (int q = 0; q < kSlTargets; ++q) {
-                        const u64 kk = q < kSlTargets - 1 ? ks[j] : ~ks[j];
-                        if (act[q] && (kk & pmask) == pf[q])
-                            atomicAdd(&sh.hist[q][(kk >> shift) & 255], 1);
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        for (int q = wave; q < kSlTargets; q += kSlThreads / 64) {   // target q on wave q % 8
-            const int need = sh.need[q];
-            if (need > 0) {
-                int d = 0, before = 0;
-                if (pick_digit(sh.hist[q], need, lane, d, before)) {
-                    sh.prefix[q] |= (u64)d << shift;
-                    sh.need[q] = need - before;
-                }
-            }
-        }
-        pmask |= 255ull << shift;
-        __syncthreads();
-    }
-    // ties at each target's key: the need-th smallest position among them, by the same select
-    // over the positions (16 bits: two byte passes)
-    {
-        int epfx[kSlTargets];
-#pragma unroll
-        for (int q = 0; q < kSlTargets; ++q) epfx[q] = 0;
-        int emask = 0;
-        for (int shift = 8; shift >= 0; shift -= 8) {
-            for (int e = tid; e < kSlTargets * 256; e += kSlThreads) (&sh.hist[0][0])[e] = 0;
-            u64 pf[kSlTargets];
-            bool act[kSlTargets];
-#pragma unroll
-            for (int q = 0; q < kSlTargets; ++q) {
-                pf[q] = sh.prefix[q];
-                act[q] = sh.need[q] > 0;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < NR; ++j) {
-                const int e = j * kSlThreads + tid;
-                if ((keyed >> j) & 1) {
-#pragma unroll
-                    for (int q = 0; q < kSlTargets; ++q) {
-                        const u64 kk = q < kSlTargets - 1 ? ks[j] : ~ks[j];
-                        if (act[q] && kk == pf[q] && (e & emask) == epfx[q])
-                            atomicAdd(&sh.hist[q][(e >> shift) & 255], 1);
-                    }
-                }
-            }
-            __syncthreads();
-            for (int q = wave; q < kSlTargets; q += kSlThreads / 64) {
-                const int need = sh.need[q];
-                if (need > 0) {
-                    int d = 0, before = 0;
-                    if (pick_digit(sh.hist[q], need, lane, d, before)) {
-                        sh.eqidx[q] = (shift == 8 ? 0 : sh.eqidx[q]) | (d << shift);
-                        sh.need[q] = need - before;
-                    }
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int q = 0; q < kSlTargets; ++q) epfx[q] = sh.need[q] > 0 ? sh.eqidx[q] : 0;
-            emask |= 255 << shift;
-            __syncthreads();
-        }
-    }
+    decile_select<NR, kSlThreads, 8>(sh.sel, ks, keyed, nk, tid);
     // every row's layer = 1 + the decile bounds below it; the top rows (key descending, position
     // ascending, up to the 10th)
     {
-        u64 kq[kSlTargets];
-        int iq[kSlTargets];
-        bool has[kSlTargets];
+        u64 kq[kSelTargets];
+        int iq[kSelTargets];
+        bool has[kSelTargets];
 #pragma unroll
-        for (int q = 0; q < kSlTargets; ++q) {
-            kq[q] = sh.prefix[q];
-            iq[q] = sh.eqidx[q];
-            has[q] = sh.rneed[q] > 0;
+        for (int q = 0; q < kSelTargets; ++q) {
+            kq[q] = sh.sel.prefix[q];
+            iq[q] = sh.sel.eqidx[q];
+            has[q] = sh.sel.rneed[q] > 0;
         }
 #pragma unroll
         for (int j = 0; j < NR; ++j) {
@@ -348,11 +197,11 @@ __global__ __launch_bounds__(kSlThreads, NR <= kSlFewKeys ? 4 : 2) void screen_l
             if ((keyed >> j) & 1) {
                 int l = 0;
 #pragma unroll
-                for (int q = 0; q < kSlTargets - 1; ++q)
+                for (int q = 0; q < kSelTargets - 1; ++q)
                     l += !has[q] || ks[j] > kq[q] || (ks[j] == kq[q] && e > iq[q]) ? 1 : 0;
                 slay[e] = (int8_t)l;
                 const u64 kd = ~ks[j];                     // descending order key
-                const int q = kSlTargets - 1;
+                const int q = kSelTargets - 1;
                 if (kd < kq[q] || (kd == kq[q] && e <= iq[q])) {
                     const int s = atomicAdd(&sh.ntop, 1);
                     if (s < kSlTopK) {

@@ -6,8 +6,9 @@
 //  turnover_marks_kernel    one workgroup per (evaluated date, column), once whatever the lags
 //                           are.  The column's values gathered through rows_idx (z-scored on the
 //                           way when zs is given), their order keys sorted run by run -- keys
-//                           only, rank_ic_kernel's scheme (rankic.hip) including its scratch path
-//                           above kTvLdsRows rows; a NaN sorts as the pad key and has no rank --
+//                           only, afm_order.h's run sort as in rank_ic_kernel, including the
+//                           scratch path above kSortLdsRows rows; a NaN sorts as the pad key and
+//                           has no rank --
 //                           and every row finds the bounds [lb, ub) of its own key.  It leaves the
 //                           date's marks in the caller's scratch:
 //                             ranks   int32 [lda] by asset: 2 * rank = lb + ub + 1, 0 = no rank;
@@ -42,126 +43,27 @@
 #pragma clang fp contract(off)
 
 #include "afm_np_sum.h"                // qnan
+#include "afm_order.h"                 // okey, layer_of, sort_rows, bounds
 
 namespace afm {
 namespace {
 
-typedef unsigned long long u64;
-typedef long long i64;
 constexpr int kTvThreads = 1024;       // 16 waves
 constexpr int kTvWaves = kTvThreads / 64;
-constexpr int kTvLdsRows = 16384;      // rows of a date sorted and searched in LDS (128 KB of keys)
-constexpr int kTvChunk = 16384;        // rows of the longest sorted run
-constexpr int kTvMinRun = 1024;        // no run is split below twice this
 constexpr int kTvMaxRows = 32768;      // afm_xs_prepare_f64's limit
 constexpr int kTvFewKeys = 4;          // rows per thread: lda up to 4096
 constexpr int kTvMidKeys = 16;         // ... up to 16384
 constexpr int kTvManyKeys = 32;        // ... up to 32768
 constexpr int kTvSlots = 256;          // workgroups of a marks launch that sorts through scratch
 constexpr int kTvBook = 10;            // rows of the top book
-constexpr int kTvLayers = 10;
 constexpr int kTvHeader = 16;          // words: {nbook | n_k << 32}, 10 weights, 5 of assets
 constexpr i64 kTvBudget = 128ll << 20; // bytes of date slots in the scratch (at least two slots)
 constexpr int kTvPairThreads = 256;    // four items a workgroup
-constexpr u64 kTvPad = ~0ull;          // above the key of every finite value and of +-inf
 constexpr unsigned kTvNoKey = ~0u;
-static_assert(kTvChunk == kTvLdsRows && (kTvChunk & (kTvChunk - 1)) == 0 &&
-              kTvChunk % (2 * kTvMinRun) == 0, "runs sort in LDS, side by side");
-static_assert(kTvManyKeys * kTvThreads == kTvMaxRows && kTvMidKeys * kTvThreads == kTvLdsRows,
+static_assert(kTvThreads == kSortThreads, "afm_order.h's sort is written for this workgroup");
+static_assert(kTvManyKeys * kTvThreads == kTvMaxRows && kTvMidKeys * kTvThreads == kSortLdsRows,
               "key capacities");
 static_assert(kTvMaxRows <= 65535 + 1, "bounds are packed in 16 bits each");
-
-__device__ __forceinline__ u64 okey(double v) {          // analyzer.hip's: -0.0 ties with 0.0
-    if (v == 0.0) v = 0.0;
-    u64 u = (u64)__double_as_longlong(v);
-    return (u >> 63) ? ~u : (u | (1ull << 63));
-}
-__device__ __forceinline__ int layer_of(int r, int n) {   // KKT:328-330
-    int l = (int)((double)r / (double)n * kTvLayers) + 1;
-    return l > kTvLayers ? kTvLayers : l;
-}
-
-__host__ __device__ __forceinline__ int pow2_at_least(int n) {
-    int p = 2;
-    while (p < n) p <<= 1;
-    return p;
-}
-
-// ---- rankic.hip's sort: runs of a power of two rows, each a bitonic network in LDS ---------------
-__device__ void bitonic_sort(u64* key, int P) {
-    const int tid = threadIdx.x;
-    for (int size = 2; size <= P; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int e = tid; e < P / 2; e += kTvThreads) {
-                const int lo = 2 * e - (e & (stride - 1));
-                const int hi = lo + stride;
-                const bool up = (lo & size) == 0;
-                const u64 ka = key[lo], kb = key[hi];
-                if ((ka > kb) == up && ka != kb) {
-                    key[lo] = kb;
-                    key[hi] = ka;
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
-__device__ __forceinline__ int run_rows(int rem) {
-    if (rem >= kTvChunk) return kTvChunk;
-    return rem >= 2 * kTvMinRun ? 1 << (31 - __clz(rem)) : rem;
-}
-
-// The keys keyfn(e), e in [0, n), sorted run by run: run [c0, c0 + len) at lds + c0 when n <=
-// kTvLdsRows (only the last run is padded), else at scr + c0.  Opens and closes with a barrier.
-template <class KeyFn>
-__device__ void sort_rows(u64* lds, u64* scr, int n, KeyFn keyfn) {
-    const int tid = threadIdx.x;
-    const bool in_lds = n <= kTvLdsRows;
-    __syncthreads();
-    for (int c0 = 0; c0 < n;) {
-        const int len = run_rows(n - c0);
-        const int P = pow2_at_least(len);
-        u64* buf = in_lds ? lds + c0 : lds;
-        for (int e = tid; e < P; e += kTvThreads) buf[e] = e < len ? keyfn(c0 + e) : kTvPad;
-        __syncthreads();
-        bitonic_sort(buf, P);
-        if (!in_lds) {
-            for (int e = tid; e < len; e += kTvThreads) scr[c0 + e] = buf[e];
-            __syncthreads();
-        }
-        c0 += len;
-    }
-}
-
-// lb += the keys of the run below k, ub += those up to k
-template <class Ptr>
-__device__ __forceinline__ void run_bounds(Ptr K, int len, u64 k, int& lb, int& ub) {
-    int lo = 0, hi = len;
-    while (lo < hi) {                                      // first key >= k
-        const int m = (lo + hi) >> 1;
-        if (K[m] < k) lo = m + 1; else hi = m;
-    }
-    lb += lo;
-    hi = len;
-    while (lo < hi) {                                      // first key > k
-        const int m = (lo + hi) >> 1;
-        if (K[m] <= k) lo = m + 1; else hi = m;
-    }
-    ub += lo;
-}
-
-__device__ __forceinline__ void bounds(const u64* lds, const u64* scr, int n, u64 k, int& lb,
-                                       int& ub) {
-    lb = 0;
-    ub = 0;
-    const u64* keys = n <= kTvLdsRows ? lds : scr;
-    for (int c0 = 0; c0 < n;) {
-        const int len = run_rows(n - c0);
-        run_bounds(keys + c0, len, k, lb, ub);
-        c0 += len;
-    }
-}
 
 // ---- marks -----------------------------------------------------------------------------------------
 // words of one (date, column) record: ranks, two bitmaps, the header
@@ -181,7 +83,7 @@ struct TvMarksArgs {
     int64_t add, mod;         // the slot of position i: (i - i0 + add) % mod
     const int32_t* rows_idx;  // [T][lda]
     const int32_t* nrows;     // [T]
-    u64* sortscr;             // [gridDim.x][lda] when lda > kTvLdsRows
+    u64* sortscr;             // [gridDim.x][lda] when lda > kSortLdsRows
     u64* marks;               // [mod][K][rec_words(lda)]
 };
 
@@ -236,12 +138,12 @@ __global__ __launch_bounds__(kTvThreads) void turnover_marks_kernel(TvMarksArgs 
         if (tid == 0) sh.nbook = 0;
         sort_rows(lds, scr, n, [&](int e) {
             const double v = fval(e);
-            return v == v ? okey(v) : kTvPad;
+            return v == v ? okey(v) : kSortPad;
         });
         int nk = 0;                                        // the ranked rows: the keys below the pad
         {
-            int lb;                                        // (kTvPad - 1 is a NaN's key: no row's)
-            bounds(lds, scr, n, kTvPad - 1, lb, nk);
+            int lb;                                        // (kSortPad - 1 is a NaN's key: no row's)
+            bounds(lds, scr, n, kSortPad - 1, lb, nk);
         }
         if (nk == 0) {                                     // (uniform) nothing ranked
             for (int w = tid; w < lda / 32; w += kTvThreads) bits[w] = 0ull;
@@ -249,7 +151,7 @@ __global__ __launch_bounds__(kTvThreads) void turnover_marks_kernel(TvMarksArgs 
             continue;
         }
         if (tid < 2) {                // the largest first-rank whose layer is <= 1 (tid 0), <= 9
-            const int l = tid == 0 ? 1 : kTvLayers - 1;
+            const int l = tid == 0 ? 1 : kOrdLayers - 1;
             int lo_ = 0, hi = nk;
             while (lo_ < hi) {
                 const int m = (lo_ + hi + 1) >> 1;
@@ -556,23 +458,23 @@ TvLayout tv_layout(int64_t nd, int K, int64_t lda) {
     y.slots = kTvBudget / per_date;
     if (y.slots < 2) y.slots = 2;
     if (y.slots > nd) y.slots = nd > 0 ? nd : 1;
-    y.sort_words = lda > kTvLdsRows ? (int64_t)kTvSlots * lda : 0;
+    y.sort_words = lda > kSortLdsRows ? (int64_t)kTvSlots * lda : 0;
     return y;
 }
 
 template <int NR>
 int launch_marks(afm_ctx* ctx, const TvMarksArgs& g) {
-    const bool chunked = g.lda > kTvLdsRows;
+    const bool chunked = g.lda > kSortLdsRows;
     const dim3 grid((unsigned)(chunked && g.items > kTvSlots ? kTvSlots : g.items));
-    const size_t lds = sizeof(u64) * (size_t)pow2_at_least((int)(g.lda < kTvLdsRows ? g.lda : kTvLdsRows));
+    const size_t lds = sizeof(u64) * (size_t)pow2_at_least((int)(g.lda < kSortLdsRows ? g.lda : kSortLdsRows));
     if (g.zs) {
         AFM_HIP(afm_lds_opt_in(ctx, (const void*)turnover_marks_kernel<NR, true>,
-                               sizeof(u64) * kTvLdsRows));
+                               sizeof(u64) * kSortLdsRows));
         hipLaunchKernelGGL((turnover_marks_kernel<NR, true>), grid, dim3(kTvThreads), lds,
                            ctx->stream, g);
     } else {
         AFM_HIP(afm_lds_opt_in(ctx, (const void*)turnover_marks_kernel<NR, false>,
-                               sizeof(u64) * kTvLdsRows));
+                               sizeof(u64) * kSortLdsRows));
         hipLaunchKernelGGL((turnover_marks_kernel<NR, false>), grid, dim3(kTvThreads), lds,
                            ctx->stream, g);
     }

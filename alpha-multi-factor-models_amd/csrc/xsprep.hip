@@ -33,12 +33,11 @@
 #pragma clang fp contract(off)
 
 #include "afm_np_sum.h"
+#include "afm_order.h"                 // okey, unkey, pick_digit
 
 namespace afm {
 namespace {
 
-typedef unsigned long long u64;
-typedef long long i64;
 constexpr int kXpThreads = 512;                    // threads per (date, column) workgroup
 constexpr int kXpFewKeys = 8;                      // register keys per thread, dates of few rows
 constexpr int kXpSmallKeys = 24;                   // ... of more
@@ -57,16 +56,6 @@ static_assert(kXpLargeKeys * kXpThreads == kXpMaxRows && kXpLargeKeys <= 64, "la
 static_assert(kXpGroups <= 256 && kXpGroups <= kXpThreads, "a group label is one byte");
 // 2^15 addends below 2^(kXpHiBits + 1) (2^kXpLoBits) stay inside a signed 64-bit limb
 static_assert(kXpHiBits + 1 + 15 < 63 && kXpLoBits + 1 + 15 < 63, "limbs cannot overflow");
-
-__device__ __forceinline__ u64 okey(double v) {    // analyzer.hip's order key (-0.0 == 0.0)
-    if (v == 0.0) v = 0.0;
-    u64 u = (u64)__double_as_longlong(v);
-    return (u >> 63) ? ~u : (u | (1ull << 63));
-}
-__device__ __forceinline__ double unkey(u64 k) {   // the value of a key
-    const u64 u = (k >> 63) ? (k & ~(1ull << 63)) : ~k;
-    return __longlong_as_double((i64)u);
-}
 
 struct XpArgs {
     const double* base;       // plane k: base + cols[k] * col_stride, [T][lda]
@@ -100,27 +89,6 @@ struct XpShared {
     double gmh[kXpGroups], gml[kXpGroups];    // the group means, double-double
     unsigned bitmap[kXpMaxRows / 32];     // assets that have a result
 };
-
-// The smallest digit d of a 256-bin histogram whose cumulative count reaches `need`, by one wave
-// (screen_layers.hip's).  True on the lane that holds d; `before` = the count of smaller digits.
-__device__ __forceinline__ bool pick_digit(const int* h, int need, int lane, int& d, int& before) {
-    const int h0 = h[4 * lane], h1 = h[4 * lane + 1], h2 = h[4 * lane + 2], h3 = h[4 * lane + 3];
-    const int s4 = h0 + h1 + h2 + h3;
-    int P = s4;                                            // inclusive prefix over lanes
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(P, o, 64);
-        if (lane >= o) P += v;
-    }
-    const u64 m = __ballot(P >= need);
-    if (!m || lane != __builtin_ctzll(m)) return false;
-    int acc = P - s4;
-    if (acc + h0 >= need) { d = 4 * lane; }
-    else if (acc + h0 + h1 >= need) { d = 4 * lane + 1; acc += h0; }
-    else if (acc + h0 + h1 + h2 >= need) { d = 4 * lane + 2; acc += h0 + h1; }
-    else { d = 4 * lane + 3; acc += h0 + h1 + h2; }
-    before = acc;
-    return true;
-}
 
 // The keys of the 1-based ranks sh.need[q] (0: no such target) among the keyed rows, ascending,
 // into sh.prefix[q].  DEV: the rows' keys are those of |x - med|.  Enters and leaves synchronised.

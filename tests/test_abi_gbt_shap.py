@@ -67,7 +67,9 @@ def test_header_guard_and_limit_and_the_gbt_header_is_untouched():
     gbt = open(os.path.join(ROOT, "include", "afm_gbt.h")).read()
     assert "shap" not in gbt and "cover" not in gbt
     mk = open(os.path.join(ROOT, "alpha-multi-factor-models_amd", "Makefile")).read()
-    assert mk.count("$(INC)/afm_gbt_shap.h") == 3
+    # the two object rules and the prof rule depend on every public header, this one included
+    assert mk.count("$(wildcard $(INC)/*.h)") == 3 and "INC := $(HERE)../include" in mk
+    assert not re.search(r"\$\(INC\)/afm\w*\.h", mk)
 
 
 def test_shap_table_is_disjoint_and_layered_on_the_mlp_tables():
