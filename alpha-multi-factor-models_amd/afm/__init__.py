@@ -23,6 +23,10 @@ Drop-in Python surface (same names, arguments and results as the reference):
                                                     ``predict(X, pred_contribs=True)``: the exact
                                                     TreeSHAP contributions, the bias last
 * ``PortfolioManager(...)``                       -- KKT:795-970
+* ``RiskParams`` / ``RiskModel`` (``Pipeline.risk_fit``) -- the multi-factor risk model behind the
+                                                    reference's sample covariance (KKT:858-859):
+                                                    EWMA factor and specific risk, book risk,
+                                                    weights from B F B' + D
 * ``split_zscore(all_df)``                       -- KKT:424-458 (z-score + split)
 
 All compute runs in hand-written HIP kernels (libafm.so, C-ABI in include/afm.h); there is no
@@ -41,6 +45,7 @@ from .turnover import Turnover, factor_turnover, turnover_grid  # noqa: F401
 from .gbt import GBTModel, GBTParams, GBTRegressor  # noqa: F401
 from .mlp import MLPModel, MLPParams, MLPRegressor  # noqa: F401
 from .portfolio import PortfolioManager, mean_variance_weights  # noqa: F401
+from .risk import RiskModel, RiskParams, bias_statistic, cov_weights  # noqa: F401
 from .zscore import split_zscore, zscore_grid  # noqa: F401
 
 __all__ = ["compute_factors", "factor_panel", "FACTOR_NAMES", "PanelGrid", "pack_bits",
@@ -49,4 +54,5 @@ __all__ = ["compute_factors", "factor_panel", "FACTOR_NAMES", "PanelGrid", "pack
            "select_factors", "PortfolioManager", "split_zscore", "zscore_grid", "XsPrep",
            "preprocess_factors", "preprocess_grid", "ICWeights", "ic_weights", "combine_grid",
            "combine_factors", "Turnover", "turnover_grid", "factor_turnover", "GBTParams",
-           "GBTModel", "GBTRegressor", "MLPParams", "MLPModel", "MLPRegressor"]
+           "GBTModel", "GBTRegressor", "MLPParams", "MLPModel", "MLPRegressor", "RiskParams",
+           "RiskModel", "bias_statistic", "cov_weights"]

@@ -1443,6 +1443,119 @@ class Pipeline:
                                          np.asarray(self.full.ids)[a]], names=["date", "id"])
         return pd.DataFrame({"pred": h[t, a]}, index=idx)
 
+    # ---- the factor risk model (afm.risk, include/afm_risk.h; one GPU) ----------------------------
+    def risk_fit(self, params=None, features=None, rows: str = "z"):
+        """The multi-factor risk model (``afm.risk``) on the last ``step()``'s panel (one GPU): the
+        per-date regressions of the target plane on the raw planes ``features`` (default:
+        ``cfg.fm_features``, the Fama-MacBeth design) over the z-score rows (``rows="z"``) or the
+        all_df rows (``rows="alldf"``) of ALL dates -- its own afm_xs_gram_f64 + afm_ols_solve_f64,
+        the step's FM buffers are not touched -- then the EWMA factor covariance, the residuals and
+        the EWMA specific variance.  Runs on the caller's stream.  Returns a ``RiskModel``; the
+        device results (the residual plane among them) stay in ``self.risk``."""
+        import torch
+        from .risk import RiskModel, _check_factors, _check_params, fit_device
+        if self.W > 1:
+            raise NotImplementedError("risk_fit() runs on one GPU (world = 1)")
+        params = _check_params(params)
+        if rows not in ("z", "alldf"):
+            raise ValueError(f"rows={rows!r}: expected 'z' or 'alldf'")
+        names = list(self.cfg.fm_features) if features is None else [str(f) for f in features]
+        unknown = [f for f in names if f not in COL]
+        if unknown or len(set(names)) != len(names):
+            raise ValueError(f"features: unknown or repeated columns {unknown}")
+        _check_factors(len(names))
+        if not self._stepped:
+            raise ValueError("risk_fit(): run step() first (the panel is empty)")
+        T, lda, dev = self.T, self.lda, self.out.device
+        with self.ctx.on(torch.cuda.current_stream(dev)):                    # the caller's stream
+            res = fit_device(self.out, [COL[f] for f in names], TARGET,
+                             self.zrows if rows == "z" else self.alldf, params, T=T, A=self.A,
+                             lda=lda, col_stride=T * lda, tol=self.cfg.tol)
+        self.risk = res
+        return RiskModel(params, names, self.full.dates, self.full.ids, res)
+
+    def _risk_model(self, model, what):
+        from .risk import RiskModel
+        if not isinstance(model, RiskModel):
+            raise TypeError(f"model: expected a RiskModel, got {type(model).__name__}")
+        if tuple(model["fcov"].shape[:1]) != (self.T,) or tuple(model["spec"].shape) != \
+                (self.T, self.lda):
+            raise ValueError(f"{what}: the model was fit on another panel than this pipeline's")
+        if not self._stepped:
+            raise ValueError(f"{what}: run step() first (the panel is empty)")
+
+    def book_risk(self, model, reb=None):
+        """The books of a rebalance (default: the last step's, ``self.reb``) priced by ``model`` at
+        the rebalance dates (one GPU).  Returns a frame per date: the predicted volatility (the
+        square root of the variance per period) ``long_vol`` / ``long_factor_vol`` /
+        ``long_specific_vol`` and the same for ``short_`` and ``net_`` (the net book is
+        (long - short) / 2), ``long_filled`` ... (members priced at the date's mean specific
+        variance), ``status`` (4: the model has no forecast for the date), and ``contrib``: a frame
+        with the columns (book, factor), the factors' contributions to the factor variance.  The
+        device results stay in ``self.risk_books``."""
+        import pandas as pd
+        import torch
+        from .risk import book_risk_device
+        if self.W > 1:
+            raise NotImplementedError("book_risk() runs on one GPU (world = 1)")
+        self._risk_model(model, "book_risk()")
+        reb = self.reb if reb is None else reb
+        dev = self.out.device
+        with self.ctx.on(torch.cuda.current_stream(dev)):
+            out = book_risk_device(model.planes, self.out, reb, self.rdates, T=self.T,
+                                   lda=self.lda, kc=max(int(self.cfg.top_n), 1),
+                                   col_stride=self.T * self.lda)
+        self.risk_books = out
+        risk, contrib = out["risk"].cpu().numpy(), out["contrib"].cpu().numpy()
+        dates = pd.Index(np.asarray(self.full.dates)[self.rdates.cpu().numpy()], name="date")
+        cols = {}
+        with np.errstate(all="ignore"):
+            for s, book in enumerate(("long", "short", "net")):
+                for j, part in enumerate(("vol", "factor_vol", "specific_vol")):
+                    cols[f"{book}_{part}"] = np.sqrt(risk[:, s, j])
+                cols[f"{book}_filled"] = risk[:, s, 3]
+        cols["status"] = out["status"].cpu().numpy()
+        frame = pd.DataFrame(cols, index=dates)
+        ci = pd.MultiIndex.from_product([("long", "short", "net"), model.factors],
+                                        names=["book", "factor"])
+        frame.attrs["contrib"] = pd.DataFrame(contrib.reshape(len(dates), -1), index=dates,
+                                              columns=ci)
+        return frame
+
+    def risk_rebalance(self, model, risk_tolerance: float = 0.0, mu=None, v0=None, rate=None):
+        """The rebalance with the model's covariance in place of the sample covariance (one GPU):
+        the existing rebalance for the selection (and the sample-covariance weights), the books'
+        covariance B F B' + D, every book's weights solved again from it, then the PnL scan.
+        ``risk_tolerance`` > 0 adds the return term with ``mu`` a [T][lda] device plane (default:
+        the prediction plane).  A date the model has no forecast for keeps the sample-covariance
+        weights (status bit 4).  Returns a dict of device tensors: the rebalance arrays (k, books,
+        weights, sums, upos, usize, status), the scan's (value, turnover, long_ret, short_ret) and
+        ``cov`` / ``cov_status``; ``self.reb`` and ``self.pnl`` are not touched."""
+        import torch
+        from .portfolio import pnl_scan, rebalance
+        from .risk import book_risk_device, rebalance_cov_device
+        if self.W > 1:
+            raise NotImplementedError("risk_rebalance() runs on one GPU (world = 1)")
+        self._risk_model(model, "risk_rebalance()")
+        c, sp, full, dev = self.cfg, self.sp, self.full, self.out.device
+        gamma = float(risk_tolerance)
+        if not gamma >= 0 or not np.isfinite(gamma):
+            raise ValueError(f"risk_tolerance={risk_tolerance!r}: expected a finite number >= 0")
+        mu = (self.pred if mu is None else mu) if gamma > 0 else None
+        kc = max(int(c.top_n), 1)
+        with self.ctx.on(torch.cuda.current_stream(dev)):
+            reb = rebalance(self.pred, full.tbits, self.target, self.zrows_full, full.close,
+                            self.tmr, self.rdates, A=full.A, top_n=c.top_n, window=c.window,
+                            h_range=(0, sp.tr1), lo=c.lo, hi=c.hi)
+            cv = book_risk_device(model.planes, self.out, reb, self.rdates, T=self.T, lda=self.lda,
+                                  kc=kc, col_stride=self.T * self.lda)
+            rebalance_cov_device(reb, cv["cov"], self.rdates, full.close, self.tmr, kc=kc,
+                                 cov_status=cv["status"], mu=mu, risk_tolerance=gamma, lo=c.lo,
+                                 hi=c.hi)
+            res = pnl_scan(reb, c.v0 if v0 is None else v0, c.rate if rate is None else rate)
+        res.update(reb, cov=cv["cov"], cov_status=cv["status"])
+        return res
+
     def summary(self) -> dict:
         """Host copies of the headline results (after a synchronize)."""
         v = self.pnl["value"].cpu().numpy()

@@ -2471,6 +2471,166 @@ __global__ __launch_bounds__(64) void pair_union_kernel(int64_t steps, const int
     }
 }
 
+// ---- the solves from a supplied covariance (include/afm_risk.h) -----------------------------------
+// The covariance phase of weights_kernel / rebalance_kernel replaced by a load of S into LDS; what
+// follows is their code: the same qp_setup / qp_wave / qp_block instantiations, the same trivial
+// branches, the same two summation orders of the sums.
+
+// numpy's pairwise sum of n <= 128 values (one leaf): pairwise_dense's arithmetic, a copy of its own
+// so that the rebalance kernels keep their callers (see pairwise_dense)
+__device__ double leaf_dense_cov(const double* a, int n) {
+    if (n < 8) {
+        double res = 0.;
+        for (int i = 0; i < n; ++i) res += a[i];
+        return res;
+    }
+    double r[8];
+    for (int j = 0; j < 8; ++j) r[j] = a[j];
+    int i;
+    for (i = 8; i < n - (n % 8); i += 8)
+        for (int j = 0; j < 8; ++j) r[j] += a[i + j];
+    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < n; ++i) res += a[i];
+    return res;
+}
+
+// the lower triangle of cov [k][k] (row stride ld) -> sh.S
+template <int KM>
+__device__ __forceinline__ void load_cov(Shared<KM>& sh, const double* cov, const int k,
+                                         const int64_t ld) {
+    for (int e = threadIdx.x; e < k * k; e += kT) {
+        const int i = e / k, j = e - i * k;
+        if (i >= j) sh.S[tri(i, j)] = cov[i * ld + j];
+    }
+}
+
+template <bool MV>
+__global__ __launch_bounds__(kT) void cov_weights_kernel(const double* cov, int k, double lo,
+                                                         double hi, double* w, int32_t* status,
+                                                         const double* mu, double gamma) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    using Lds = typename std::conditional<MV, SharedMV<kMaxK>, Shared<kMaxK>>::type;
+    Lds& lds = *reinterpret_cast<Lds*>(smem_raw);
+    Shared<kMaxK>& sh = lds;
+    const int tid = threadIdx.x;
+    load_cov(sh, cov, k, k);
+    if constexpr (MV) {
+        if (tid < k) {
+            const double v = mu[tid];
+            lds.gm[tid] = __builtin_isfinite(v) ? gamma * v : 0.0;
+        }
+    }
+    __syncthreads();
+    bool capped = false;
+    if (k * hi <= 1.0) {
+        if (tid < k) sh.w[tid] = hi;
+    } else if (k * lo >= 1.0) {
+        if (tid < k) sh.w[tid] = lo;
+    } else if (k <= 32) {
+        const bool ok = qp_setup(sh, k);
+        if (!ok) capped = true;
+        else if (tid < 64) capped = qp_wave<kMaxK, MV>(sh, k, lo, hi);
+    } else {
+        capped = qp_block<kMaxK, MV>(sh, k, lo, hi, nullptr);
+    }
+    __syncthreads();
+    if (tid < k) w[tid] = sh.w[tid];
+    if (tid == 0) status[0] = capped ? 1 : 0;
+}
+
+struct RebCovArgs {
+    int64_t T, lda, nd;
+    const int32_t* dates;
+    const int32_t* k;
+    const int32_t* books;      // [nd][2][kMaxK]
+    const double* cov;         // [nd][2][kc][kc]
+    int kc;
+    const int32_t* cov_status; // [nd] or null
+    const double* mu;          // [T][lda] or null
+    double gamma, lo, hi;
+    const double* close;
+    const double* tmr;
+    double* weights;           // [nd][2][kMaxK]
+    double* sums;              // [nd][4]
+    int32_t* status;           // [nd]
+};
+
+// the date is solved again: a valid book size, no oversize book, a usable covariance
+__device__ __forceinline__ bool cov_date_runs(const RebCovArgs& r, int64_t i, int kmax) {
+    const int k = r.k[i];
+    const int64_t t = r.dates[i];
+    return k > 0 && k <= r.kc && k <= kmax && t >= 0 && t < r.T && !(r.status[i] & 2) &&
+           !(r.cov_status && (r.cov_status[i] & 4));
+}
+
+// before the solves: bit 1 of the dates that are solved again is theirs to set; bit 4 from the
+// covariance's status
+__global__ __launch_bounds__(256) void cov_status_kernel(RebCovArgs r, int kmax) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= r.nd) return;
+    const int32_t st = r.status[i];
+    if (r.cov_status && (r.cov_status[i] & 4)) r.status[i] = st | 4;
+    else if (cov_date_runs(r, i, kmax)) r.status[i] = st & ~1;
+}
+
+template <int KM, bool MV>
+__global__ __launch_bounds__(kT) void rebalance_cov_kernel(RebCovArgs r) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    using Lds = typename std::conditional<MV, SharedMV<KM>, Shared<KM>>::type;
+    Lds& lds = *reinterpret_cast<Lds*>(smem_raw);
+    Shared<KM>& sh = lds;
+    const int tid = threadIdx.x;
+    const int64_t i = blockIdx.x;
+    const int side = blockIdx.y;
+    if (!cov_date_runs(r, i, KM)) return;              // uniform (bit 1 is the only one in flight)
+    const int k = r.k[i];
+    const int64_t t = r.dates[i];
+    if (tid < k) {
+        const int a = r.books[(i * 2 + side) * kMaxK + tid];
+        sh.book[tid] = a >= 0 && a < r.lda ? a : 0;    // loads always in bounds
+    }
+    load_cov(sh, r.cov + (i * 2 + side) * (int64_t)r.kc * r.kc, k, r.kc);
+    __syncthreads();
+    const int* bk = sh.book;
+    if constexpr (MV) {
+        const double gs = side == 0 ? r.gamma : -r.gamma;
+        if (tid < k) {
+            const double v = r.mu[t * r.lda + bk[tid]];
+            lds.gm[tid] = __builtin_isfinite(v) ? gs * v : 0.0;
+        }
+        __syncthreads();
+    }
+    bool capped = false;
+    if (k * r.hi <= 1.0) {
+        if (tid < k) sh.w[tid] = r.hi;
+    } else if (k * r.lo >= 1.0) {
+        if (tid < k) sh.w[tid] = r.lo;
+    } else {
+        if constexpr (KM == kMaxK) {
+            capped = qp_block<KM, MV>(sh, k, r.lo, r.hi, nullptr);
+        } else {
+            const bool ok = qp_setup(sh, k);
+            if (!ok) capped = true;
+            else if (tid < 64) capped = qp_wave<KM, MV>(sh, k, r.lo, r.hi);
+        }
+    }
+    if (capped && tid == 0) atomicOr(&r.status[i], 1);
+    __syncthreads();
+    if (tid < k) {
+        r.weights[(i * 2 + side) * kMaxK + tid] = sh.w[tid];
+        const double tw = r.tmr[t * r.lda + bk[tid]] * sh.w[tid];   // tmr * w (book order)
+        sh.x[tid] = tw == tw ? tw : 0.0;                            // nansum
+        sh.c[tid] = sh.w[tid] * r.close[t * r.lda + bk[tid]];       // w * price
+    }
+    __syncthreads();
+    if (tid == 0) {
+        r.sums[i * 4 + side] = leaf_dense_cov(sh.x, k);
+        double den = 0.0;                                           // builtin sum(): 0 + ...
+        for (int a = 0; a < k; ++a) den = den + sh.c[a];
+        r.sums[i * 4 + 2 + side] = den;
+    }
+}
+
 }  // namespace
 }  // namespace afm
 
@@ -2750,4 +2910,66 @@ extern "C" int afm_bootstrap_pnl_f64(afm_ctx* ctx, int64_t lda, const int32_t* d
                        sums, rec, rlen, v0, rate, value, turnover, long_ret, short_ret, path);
     AFM_HIP(hipGetLastError());
     return AFM_OK;
+}
+
+// ---- include/afm_risk.h: the solves from a supplied covariance ---------------------------------
+#include "afm_risk.h"
+
+extern "C" int afm_cov_weights_f64(afm_ctx* ctx, const double* cov, int k, const double* mu,
+                                   double gamma, double lo, double hi, double* w,
+                                   int32_t* status) {
+    AFM_CTX(ctx);
+    AFM_CHECK_ARG(gamma >= 0.0 && std::isfinite(gamma), "gamma must be finite and >= 0");
+    AFM_CHECK_ARG(k >= 1 && k <= kMaxK, "need 1 <= k <= 128");
+    AFM_CHECK_ARG(cov && w && status && lo <= hi, "bad arguments");
+    if (gamma > 0.0 && mu != nullptr) {
+        const size_t smem = sizeof(SharedMV<kMaxK>);
+        AFM_HIP(afm_lds_opt_in(ctx, (const void*)cov_weights_kernel<true>, (int)smem));
+        hipLaunchKernelGGL(cov_weights_kernel<true>, dim3(1), dim3(kT), smem, ctx->stream, cov, k,
+                           lo, hi, w, status, mu, gamma);
+    } else {                         // the min-variance problem: its kernel, bit for bit
+        const size_t smem = sizeof(Shared<kMaxK>);
+        AFM_HIP(afm_lds_opt_in(ctx, (const void*)cov_weights_kernel<false>, (int)smem));
+        hipLaunchKernelGGL(cov_weights_kernel<false>, dim3(1), dim3(kT), smem, ctx->stream, cov, k,
+                           lo, hi, w, status, (const double*)nullptr, 0.0);
+    }
+    AFM_HIP(hipGetLastError());
+    return AFM_OK;
+}
+
+template <int KM, bool MV>
+static int launch_rebalance_cov(afm_ctx* ctx, const RebCovArgs& r) {
+    hipLaunchKernelGGL(cov_status_kernel, dim3((unsigned)((r.nd + 255) / 256)), dim3(256), 0,
+                       ctx->stream, r, KM);
+    AFM_HIP(hipGetLastError());
+    const size_t smem = MV ? sizeof(SharedMV<KM>) : sizeof(Shared<KM>);
+    AFM_HIP(afm_lds_opt_in(ctx, (const void*)rebalance_cov_kernel<KM, MV>, (int)smem));
+    hipLaunchKernelGGL((rebalance_cov_kernel<KM, MV>), dim3((unsigned)r.nd, 2), dim3(kT), smem,
+                       ctx->stream, r);
+    AFM_HIP(hipGetLastError());
+    return AFM_OK;
+}
+
+extern "C" int afm_rebalance_cov_f64(afm_ctx* ctx, int64_t T, int64_t lda, const int32_t* dates,
+                                     int64_t nd, const int32_t* k, const int32_t* books,
+                                     const double* cov, int kc, const int32_t* cov_status,
+                                     const double* mu, double gamma, double lo, double hi,
+                                     const double* close, const double* tmr, double* weights,
+                                     double* sums, int32_t* status) {
+    AFM_CTX(ctx);
+    AFM_CHECK_ARG(gamma >= 0.0 && std::isfinite(gamma), "gamma must be finite and >= 0");
+    AFM_CHECK_ARG(T > 0 && lda >= 64 && lda % 64 == 0, "bad panel shape");
+    AFM_CHECK_ARG(kc >= 1 && kc <= kMaxK, "kc must be in [max k, 128]");
+    AFM_CHECK_ARG(dates && k && books && cov && close && tmr && weights && sums && status,
+                  "null buffer");
+    AFM_CHECK_ARG(lo <= hi, "lo > hi");
+    AFM_CHECK_ARG(nd < ((int64_t)1 << 31), "nd too large for one launch");
+    if (nd <= 0) return AFM_OK;
+    const bool mv = gamma > 0.0 && mu != nullptr;
+    RebCovArgs r{T, lda, nd, dates, k, books, cov, kc, cov_status, mv ? mu : nullptr,
+                 mv ? gamma : 0.0, lo, hi, close, tmr, weights, sums, status};
+    return mv ? (kc <= 32 ? launch_rebalance_cov<32, true>(ctx, r)
+                          : launch_rebalance_cov<kMaxK, true>(ctx, r))
+              : (kc <= 32 ? launch_rebalance_cov<32, false>(ctx, r)
+                          : launch_rebalance_cov<kMaxK, false>(ctx, r));
 }
