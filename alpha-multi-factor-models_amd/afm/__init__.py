@@ -44,6 +44,7 @@ from .combine import ICWeights, combine_factors, combine_grid, ic_weights  # noq
 from .turnover import Turnover, factor_turnover, turnover_grid  # noqa: F401
 from .gbt import GBTModel, GBTParams, GBTRegressor  # noqa: F401
 from .mlp import MLPModel, MLPParams, MLPRegressor  # noqa: F401
+from .lstm import LSTMModel, LSTMParams, LSTMRegressor  # noqa: F401
 from .portfolio import PortfolioManager, mean_variance_weights  # noqa: F401
 from .risk import RiskModel, RiskParams, bias_statistic, cov_weights  # noqa: F401
 from .zscore import split_zscore, zscore_grid  # noqa: F401
@@ -55,4 +56,5 @@ __all__ = ["compute_factors", "factor_panel", "FACTOR_NAMES", "PanelGrid", "pack
            "preprocess_factors", "preprocess_grid", "ICWeights", "ic_weights", "combine_grid",
            "combine_factors", "Turnover", "turnover_grid", "factor_turnover", "GBTParams",
            "GBTModel", "GBTRegressor", "MLPParams", "MLPModel", "MLPRegressor", "RiskParams",
-           "RiskModel", "bias_statistic", "cov_weights"]
+           "RiskModel", "bias_statistic", "cov_weights", "LSTMParams", "LSTMModel",
+           "LSTMRegressor"]

@@ -10,8 +10,9 @@ number generator on the device: ``glorot_init`` draws Keras's default initial we
 ``Pipeline.mlp_fit`` calls on the resident panel), ``MLPModel`` holds the fitted ensemble on the
 host and ``MLPRegressor`` is the frame / array interface.
 
-Out of scope: the reference's LSTMs; dropout, other optimisers, shuffling; one model over several
-workgroups; the multi-GPU pipeline; fp32 or lower-precision training.
+The reference's stacked LSTMs are ``afm.lstm``.  Out of scope here: dropout, other optimisers,
+shuffling; one model over several workgroups; the multi-GPU pipeline; fp32 or lower-precision
+training.
 """
 from __future__ import annotations
 

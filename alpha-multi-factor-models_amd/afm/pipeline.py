@@ -43,6 +43,7 @@ All buffers are allocated once; a step does no host synchronisation.
 """
 from __future__ import annotations
 
+import operator
 from dataclasses import dataclass
 
 import numpy as np
@@ -1331,6 +1332,69 @@ class Pipeline:
         keep = set(top) | {f for f, b in zip(self.features, beta[1:]) if b != 0}
         return [f for f in self.features if f in keep]
 
+    def _net_fit_rows(self, rt, ra, what):
+        """The train / eval rows of the network fits (``mlp_fit``, ``lstm_fit``) from the date-major
+        rows (rt, ra) of the dates [0, v1): the rows of the dates [0, tr1), then those of [tr1 -
+        dup, v1), without the rows that have no finite label.  -> rt, ra, y [n], n_train."""
+        import torch
+        sp, T, lda, dev = self.sp, self.T, self.lda, self.out.device
+        ev = rt >= sp.tr1 - int(bool(sp.dup))
+        tr = rt < sp.tr1
+        rt = torch.cat([rt[tr], rt[ev]]).contiguous()
+        ra = torch.cat([ra[tr], ra[ev]]).contiguous()
+        n_train, n = int(tr.sum()), int(rt.numel())
+        y = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+        tcol = torch.tensor([TARGET], dtype=torch.int32, device=dev)
+        if n:
+            self.ctx.call("afm_gbt_values_f64", self.out, T * lda, T, lda, tcol, 0, None, rt,
+                          ra, n, y)
+        ok = torch.isfinite(y[:n])
+        if not bool(ok.all()):                   # a row without a label neither trains nor scores
+            n_train = int(ok[:n_train].sum())
+            rt, ra, y = rt[ok].contiguous(), ra[ok].contiguous(), y[:n][ok]
+        if n_train == 0:
+            raise ValueError(f"{what}(): the split has no z-score rows to train on")
+        return rt, ra, y[:int(rt.numel())], n_train
+
+    def _net_fit(self, rt, ra, what, planes, fit_device, params):
+        """A network fit on the rows of ``_net_fit_rows``: ``planes(rt, ra, n_pad)`` builds the
+        design, the label is zero padded.  -> the device results of ``fit_device`` with the rows,
+        ``X``, ``y``, ``n_train`` and ``n_eval`` added."""
+        import torch
+        rt, ra, y, n_train = self._net_fit_rows(rt, ra, what)
+        n = int(rt.numel())
+        n_pad = (n + 63) // 64 * 64
+        X = planes(rt, ra, n_pad)
+        yp = torch.zeros(n_pad, dtype=torch.float64, device=self.out.device)
+        yp[:n] = y
+        res = fit_device(X, yp, n_train, n - n_train, params)
+        res.update(rows_t=rt, rows_a=ra, X=X, y=yp, n_train=n_train, n_eval=n - n_train)
+        return res
+
+    def _net_predict(self, rt, ra, planes, forward, member, frame):
+        """The prediction plane [T][lda] of a network ensemble on those of the date-major rows (rt,
+        ra) that lie in the test dates -- ``forward(planes(rt, ra, n_pad), n)`` -> [M][n_pad], the
+        member or the member mean scattered, NaN everywhere else -- or, with ``frame``, the (date,
+        id)-indexed one-column frame ('pred')."""
+        import torch
+        T, lda, dev = self.T, self.lda, self.out.device
+        pred = torch.full((T, lda), float("nan"), dtype=torch.float64, device=dev)
+        te = rt >= self.sp.s0
+        rt, ra = rt[te].contiguous(), ra[te].contiguous()
+        n = int(rt.numel())
+        if n:
+            out = forward(planes(rt, ra, (n + 63) // 64 * 64), n)
+            val = out[member, :n] if member is not None else out[:, :n].mean(dim=0)
+            pred[rt.long(), ra.long()] = val
+        if not frame:
+            return pred
+        import pandas as pd
+        h = pred[:, :self.A].cpu().numpy()
+        t, a = np.nonzero(~np.isnan(h))
+        idx = pd.MultiIndex.from_arrays([np.asarray(self.full.dates)[t],
+                                         np.asarray(self.full.ids)[a]], names=["date", "id"])
+        return pd.DataFrame({"pred": h[t, a]}, index=idx)
+
     def _mlp_columns(self, features):
         """The indices into ``self.features`` of the named columns (default: all)."""
         if features is None:
@@ -1377,32 +1441,12 @@ class Pipeline:
             raise ValueError("mlp_fit(): run step() first (the panel is empty)")
         idx = self._mlp_columns(features)
         _check_shape(len(idx), params.hidden)
-        sp, T, lda, dev = self.sp, self.T, self.lda, self.out.device
+        dev = self.out.device
         with self.ctx.on(torch.cuda.current_stream(dev)):                    # the caller's stream
-            rt, ra = self._gbt_rows(sp.v1)
-            ev = rt >= sp.tr1 - int(bool(sp.dup))
-            tr = rt < sp.tr1
-            rt = torch.cat([rt[tr], rt[ev]]).contiguous()
-            ra = torch.cat([ra[tr], ra[ev]]).contiguous()
-            n_train, n = int(tr.sum()), int(rt.numel())
-            y = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
-            tcol = torch.tensor([TARGET], dtype=torch.int32, device=dev)
-            if n:
-                self.ctx.call("afm_gbt_values_f64", self.out, T * lda, T, lda, tcol, 0, None, rt,
-                              ra, n, y)
-            ok = torch.isfinite(y[:n])
-            if not bool(ok.all()):                   # a row without a label neither trains nor scores
-                n_train = int(ok[:n_train].sum())
-                rt, ra, y = rt[ok].contiguous(), ra[ok].contiguous(), y[:n][ok]
-                n = int(rt.numel())
-            if n_train == 0:
-                raise ValueError("mlp_fit(): the split has no z-score rows to train on")
-            n_pad = (n + 63) // 64 * 64
-            X = self._mlp_planes(idx, rt, ra, n_pad)
-            yp = torch.zeros(n_pad, dtype=torch.float64, device=dev)
-            yp[:n] = y[:n]
-            res = fit_device(X, yp, n_train, n - n_train, params)
-            res.update(rows_t=rt, rows_a=ra, X=X, y=yp, n_train=n_train, n_eval=n - n_train)
+            rt, ra = self._gbt_rows(self.sp.v1)
+            res = self._net_fit(rt, ra, "mlp_fit",
+                                lambda t, a, n_pad: self._mlp_planes(idx, t, a, n_pad), fit_device,
+                                params)
             self.mlp = res
             return MLPModel.from_device(res, params, [self.features[k] for k in idx])
 
@@ -1422,26 +1466,119 @@ class Pipeline:
             raise ValueError("mlp_predict(): run step() first (the panel is empty)")
         idx = self._mlp_columns(model.features)
         member = _member(model, member)
-        sp, T, lda, dev = self.sp, self.T, self.lda, self.out.device
-        pred = torch.full((T, lda), float("nan"), dtype=torch.float64, device=dev)
+        dev = self.out.device
         with self.ctx.on(torch.cuda.current_stream(dev)):
-            rt, ra = self._gbt_rows(T)
-            te = rt >= sp.s0
-            rt, ra = rt[te].contiguous(), ra[te].contiguous()
-            n = int(rt.numel())
-            if n:
-                X = self._mlp_planes(idx, rt, ra, (n + 63) // 64 * 64)
-                out = forward_device(X, model.device_theta(dev), model.params.hidden, 0, n)
-                val = out[member, :n] if member is not None else out[:, :n].mean(dim=0)
-                pred[rt.long(), ra.long()] = val
-        if not frame:
-            return pred
-        import pandas as pd
-        h = pred[:, :self.A].cpu().numpy()
-        t, a = np.nonzero(~np.isnan(h))
-        idx = pd.MultiIndex.from_arrays([np.asarray(self.full.dates)[t],
-                                         np.asarray(self.full.ids)[a]], names=["date", "id"])
-        return pd.DataFrame({"pred": h[t, a]}, index=idx)
+            rt, ra = self._gbt_rows(self.T)
+            return self._net_predict(
+                rt, ra, lambda t, a, n_pad: self._mlp_planes(idx, t, a, n_pad),
+                lambda X, n: forward_device(X, model.device_theta(dev), model.params.hidden, 0, n),
+                member, frame)
+
+    # ---- stacked LSTM ensembles (afm.lstm, include/afm_lstm.h; one GPU) ----------------------------
+    def _lstm_rows(self, t1, lookback):
+        """(rows_t, rows_a) int32, date-major: the z-score rows of the dates [0, t1) -- with
+        ``lookback=L`` only those whose asset has a z-score row on all of the L dates up to
+        theirs."""
+        import torch
+        rt, ra = self._gbt_rows(t1)
+        if lookback is None:
+            return rt, ra
+        m = torch.zeros((t1, self.zrows.shape[1]), dtype=torch.bool, device=rt.device)
+        m[rt.long(), ra.long()] = True
+        win = m.clone()
+        for k in range(1, lookback):
+            win[k:] &= m[:t1 - k]
+        win[:lookback - 1] = False
+        idx = torch.nonzero(win)
+        return idx[:, 0].to(torch.int32).contiguous(), idx[:, 1].to(torch.int32).contiguous()
+
+    def _lstm_planes(self, idx, rt, ra, n_pad, lookback):
+        """The z-scored sequences of the rows (rt, ra) as planes [T][d][n_pad], zero padded.
+        ``lookback=None``: T = len(idx), d = 1 -- ``_mlp_planes``' output; ``lookback=L``: plane
+        (t, j) is column idx[j] at the date L - 1 - t before the row's, gathered with
+        afm_gbt_values_f64 on the shifted row list."""
+        import torch
+        if lookback is None:
+            return self._mlp_planes(idx, rt, ra, n_pad).view(len(idx), 1, n_pad)
+        T, lda, n = self.T, self.lda, int(rt.numel())
+        X = torch.zeros((lookback, len(idx), n_pad), dtype=torch.float64, device=self.out.device)
+        for t in range(lookback):
+            st = (rt - (lookback - 1 - t)).contiguous()
+            for j, k in enumerate(idx):
+                self.ctx.call("afm_gbt_values_f64", self.out, T * lda, T, lda, self.feat, k,
+                              self.zs, st, ra, n, X[t, j])
+        return X
+
+    def _lstm_layout(self, n_features, lookback):
+        from .lstm import MAX_STEPS, _check_shape
+        if lookback is not None:
+            try:
+                lookback = operator.index(lookback)
+            except TypeError:
+                raise ValueError(f"lookback={lookback!r}: expected an integer or None") from None
+            if not 1 <= lookback <= MAX_STEPS:
+                raise ValueError(f"lookback={lookback}: expected 1..{MAX_STEPS}")
+            _check_shape(lookback, n_features)
+        else:
+            _check_shape(n_features, 1)
+        return lookback
+
+    def lstm_fit(self, params=None, *, features=None, lookback=None):
+        """An ensemble of stacked LSTMs (``afm.lstm``) on the last ``step()``'s panel (one GPU):
+        the reference's LSTM -> LSTM -> Dense(1) fits (KKT:709-789) on the z-scored design, with
+        the train / eval rows of ``mlp_fit``.  ``lookback=None`` is the reference's layout: every
+        feature is one step (``T = len(features), d = 1``).  ``lookback=L``: a row is the window of
+        the last L dates of its security (``T = L, d = len(features)``); it is kept only if the
+        asset has a z-score row on all L dates.  The windows of eval rows may reach back across the
+        split boundary: features of earlier dates are not a look-ahead.
+
+        Runs on the caller's stream.  Returns a ``LSTMModel`` (it remembers ``lookback``); the
+        device results of the fit stay in ``self.lstm`` (``theta``, ``evals``, ``snaps``, ``X``,
+        ``y``, the row lists ``rows_t`` / ``rows_a``, ``n_train``, ``n_eval``)."""
+        import torch
+        from .lstm import LSTMModel, _check_params, fit_device
+        if self.W > 1:
+            raise NotImplementedError("lstm_fit() runs on one GPU (world = 1)")
+        params = _check_params(params)
+        if not self._stepped:
+            raise ValueError("lstm_fit(): run step() first (the panel is empty)")
+        idx = self._mlp_columns(features)
+        lookback = self._lstm_layout(len(idx), lookback)
+        dev = self.out.device
+        with self.ctx.on(torch.cuda.current_stream(dev)):                    # the caller's stream
+            rt, ra = self._lstm_rows(self.sp.v1, lookback)
+            res = self._net_fit(
+                rt, ra, "lstm_fit",
+                lambda t, a, n_pad: self._lstm_planes(idx, t, a, n_pad, lookback), fit_device,
+                params)
+            self.lstm = res
+            return LSTMModel.from_device(res, params, [self.features[k] for k in idx], lookback)
+
+    def lstm_predict(self, model, frame: bool = False, member=None):
+        """The networks of ``model`` over the test dates' z-score rows of the resident panel (with
+        ``model.lookback``: those with a full window, rebuilt as ``lstm_fit`` built them): a device
+        plane [T][lda] shaped like ``pipe.pred`` -- the mean over the members (default) or the
+        prediction of ``member`` on those rows, NaN everywhere else.  ``frame=True``: the (date,
+        id)-indexed one-column frame ('pred') that ``afm.AlphaSignalAnalyzer`` and
+        ``afm.PortfolioManager`` take."""
+        import torch
+        from .lstm import LSTMModel, forward_device
+        from .mlp import _member
+        if self.W > 1:
+            raise NotImplementedError("lstm_predict() runs on one GPU (world = 1)")
+        if not isinstance(model, LSTMModel):
+            raise TypeError(f"model: expected a LSTMModel, got {type(model).__name__}")
+        if not self._stepped:
+            raise ValueError("lstm_predict(): run step() first (the panel is empty)")
+        idx = self._mlp_columns(model.features)
+        member = _member(model, member)
+        dev = self.out.device
+        with self.ctx.on(torch.cuda.current_stream(dev)):
+            rt, ra = self._lstm_rows(self.T, model.lookback)
+            return self._net_predict(
+                rt, ra, lambda t, a, n_pad: self._lstm_planes(idx, t, a, n_pad, model.lookback),
+                lambda X, n: forward_device(X, model.device_theta(dev), model.params.hidden, 0, n),
+                member, frame)
 
     # ---- the factor risk model (afm.risk, include/afm_risk.h; one GPU) ----------------------------
     def risk_fit(self, params=None, features=None, rows: str = "z"):

@@ -98,6 +98,10 @@ int afm_ctx_set_option(afm_ctx* ctx, const char* name, int64_t value) {
         AFM_CHECK_ARG(value >= 0 && value <= (1 << 20),
                       "mlp_steps_per_launch: 0 (auto) or 1..2^20 steps");
         ctx->mlp_steps_per_launch = value;
+    } else if (n == "lstm_rows_per_wg") {
+        AFM_CHECK_ARG(value >= 0 && value <= 64 && value % 16 == 0,
+                      "lstm_rows_per_wg: 0 (auto), 16, 32, 48 or 64 rows");
+        ctx->lstm_rows_per_wg = (int)value;
     } else {
         AFM_CHECK_ARG(false, "unknown option " + n);
     }
@@ -114,6 +118,7 @@ int afm_ctx_get_option(afm_ctx* ctx, const char* name, int64_t* value) {
     else if (n == "gram_checked") *value = ctx->gram_checked ? 1 : 0;
     else if (n == "gbt_rows_per_wg") *value = ctx->gbt_rows_per_wg;
     else if (n == "mlp_steps_per_launch") *value = ctx->mlp_steps_per_launch;
+    else if (n == "lstm_rows_per_wg") *value = ctx->lstm_rows_per_wg;
     else AFM_CHECK_ARG(false, "unknown option " + n);
     return AFM_OK;
 }

@@ -41,6 +41,7 @@ struct afm_ctx {
     int gram_checked = 0;    // afm_xs_gram_f64: checked staging only (no FAST + REDO passes)
     int64_t gbt_rows_per_wg = 0;   // afm_gbt_hist_i64 / fit: rows of a histogram workgroup's chunk
     int64_t mlp_steps_per_launch = 0;   // afm_mlp_fit_f64: batch steps of one kernel launch
+    int lstm_rows_per_wg = 0;           // afm_lstm_*: batch rows of a recurrent-kernel workgroup
     // factor slab calls: the work split each state buffer's layout was written with (the state
     // is [block][split][wave]; a later slab under another factor_split would misread it), and
     // the lock guarding it (host threads may share a context)

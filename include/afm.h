@@ -52,7 +52,9 @@ int afm_ctx_set_stream(afm_ctx* ctx, void* stream);
  *   "gbt_rows_per_wg"  0 (default: the library's choice) | 1..2^20: rows of the chunk a workgroup
  *                   of the boosted trees' histogram kernel owns (afm_gbt.h), rounded up to 4
  *   "mlp_steps_per_launch"  0 (default: the library's choice) | 1..2^20: batch steps of every
- *                   model that one launch of the network fit runs (afm_mlp.h) */
+ *                   model that one launch of the network fit runs (afm_mlp.h)
+ *   "lstm_rows_per_wg"  0 (default: the library's choice) | 16 | 32 | 48 | 64: batch rows that a
+ *                   workgroup of the recurrent forward / backward kernels owns (afm_lstm.h) */
 int afm_ctx_set_option(afm_ctx* ctx, const char* name, int64_t value);
 /* The current value of an option of afm_ctx_set_option (value: out). */
 int afm_ctx_get_option(afm_ctx* ctx, const char* name, int64_t* value);
